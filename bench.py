@@ -9,6 +9,10 @@ on-device synthetic batch generation (Philox kernel) -> bf16-autocast forward (c
 engine's comm stream -> fused multi-tensor SGD-momentum update (fp32 master weights).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--algorithm builtin|ring|direct]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line. ``--dump-outputs DIR`` also writes
+what the last timed step computed (loss, logits, updated parameters, gradients) as DIR/<name>.npy; ``--full``
+adds what the headline figure does not need (the GPU clock / power telemetry samples around the timed region).
 For N > 1 either launch it under torchrun (python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...), or run ``python bench.py --gpus N`` as a
 plain command: with no WORLD_SIZE in the environment it starts N ranks itself (a torch.distributed.run
@@ -29,9 +33,47 @@ import sys
 import time
 
 _ROOT = os.path.dirname(os.path.abspath(__file__))
-# MIOpen find results for these conv shapes on gfx950 ship with the repo, so a fresh box skips the
-# multi-minute exhaustive search (torch.backends.cudnn.benchmark) and starts from tuned solvers.
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(_ROOT, "miopen_db"))
+
+
+def _miopen_user_db() -> str:
+    """MIOpen find results for these conv shapes on gfx950 ship with the repo (``miopen_db/``), so a fresh box
+    skips the multi-minute exhaustive search (torch.backends.cudnn.benchmark) and starts from tuned solvers.
+    MIOpen also writes to its user database, so runs work on a copy named after the shipped files' digest (a
+    changed ``miopen_db/`` starts a new copy): under the untracked ``build/``, or where that cannot be written
+    under the user's cache or temporary directory; failing all of those, on the shipped directory itself."""
+    import hashlib
+    import shutil
+    import tempfile
+
+    src = os.path.join(_ROOT, "miopen_db")
+    h = hashlib.sha256()
+    for n in sorted(os.listdir(src)):
+        h.update(n.encode() + b"\0")
+        with open(os.path.join(src, n), "rb") as f:
+            h.update(f.read())
+    name = "miopen_db-" + h.hexdigest()[:12]
+    cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    for parent in (os.path.join(_ROOT, "build"), os.path.join(cache, "distributed_learning_amd"),
+                   os.path.join(tempfile.gettempdir(), f"distributed_learning_amd-{os.getuid()}")):
+        dst = os.path.join(parent, name)
+        try:
+            if not os.path.isdir(dst):
+                os.makedirs(parent, exist_ok=True)
+                tmp = tempfile.mkdtemp(prefix=name + ".", dir=parent)
+                try:
+                    shutil.copytree(src, tmp, dirs_exist_ok=True)
+                    os.rename(tmp, dst)
+                except OSError:  # another rank got there first (checked below), or the copy failed
+                    shutil.rmtree(tmp, ignore_errors=True)
+            if os.path.isdir(dst) and os.access(dst, os.W_OK | os.X_OK):
+                return dst
+        except OSError:
+            pass
+    return src
+
+
+if "MIOPEN_USER_DB_PATH" not in os.environ:
+    os.environ["MIOPEN_USER_DB_PATH"] = _miopen_user_db()
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
@@ -119,6 +161,13 @@ def parse():
                          "barrier and rank 0 prints who joined (no GPU, no model)")
     ap.add_argument("--launch_timeout", type=float, default=3000.0,
                     help="self-launch mode: seconds before the rank processes are killed")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float32): loss, logits, and the updated parameters, their gradients and the fp32 master "
+                         "weights (tensors above a size cap as a fixed seeded sample; under 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also record what the headline figure does not need: GPU clock / power telemetry before "
+                         "warmup and around the timed region (the record's \"telemetry\")")
     return ap.parse_args()
 
 
@@ -205,7 +254,7 @@ def time_steps(step, a, dev, engine, graphed, backend, warmup=None):
     """W warmup steps (``warmup``: those not already run, default all), then exactly K timed steps between
     barrier + synchronize on both sides; the elapsed time is the MAX over ranks."""
     warmup = a.warmup if warmup is None else warmup
-    tele = {"before_warmup": telemetry.sample(dev.index or 0)}
+    tele = {"before_warmup": telemetry.sample(dev.index or 0)} if a.full else None
     # one event per step boundary (warmup and timed): the per-step GPU-stream time distribution goes into
     # the record, so a slow first-steps ramp and a uniformly slow box can be told apart
     wev = [torch.cuda.Event(enable_timing=True) for _ in range(warmup + 1)]
@@ -217,7 +266,8 @@ def time_steps(step, a, dev, engine, graphed, backend, warmup=None):
     engine.consume_comm_ms()
     engine.set_timing(not graphed)
     engine.impl.collective_counts(True)
-    tele["before_timed"] = telemetry.sample(dev.index or 0)
+    if a.full:
+        tele["before_timed"] = telemetry.sample(dev.index or 0)
     tev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
     dist.barrier()
     torch.cuda.synchronize()
@@ -231,7 +281,8 @@ def time_steps(step, a, dev, engine, graphed, backend, warmup=None):
     dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    tele["after_timed"] = telemetry.sample(dev.index or 0)
+    if a.full:
+        tele["after_timed"] = telemetry.sample(dev.index or 0)
     comm_ms = engine.consume_comm_ms() / max(1, a.steps)
     engine.set_timing(False)
     ncoll, nunits = (int(v) for v in engine.impl.collective_counts(True))
@@ -306,6 +357,52 @@ def phase_breakdown(parts, n: int, csv_path=None, name="bench"):
     if csv_path:
         et.writeout(csv_path)
     return mean
+
+
+DUMP_SAMPLE_BYTES = 48 << 20  # parameters + gradients + masters; with the logits the dump stays under 64 MB
+DUMP_LOGITS_BYTES = 8 << 20
+
+
+def dump_outputs(path, loss, logits, named_params, opt):
+    """What a caller of the timed step holds after its last call, as ``path/<name>.npy`` (float32): the loss, the
+    logits, and the updated parameters, their gradients and the optimizer's fp32 master weights, each set
+    concatenated in ``named_parameters`` order (logical NCHW element order). A tensor of more than ``cap``
+    elements contributes a fixed sample of ``cap`` of them; the sample depends only on the tensor's position
+    and size, so two builds given the same arguments write the same elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    named_params = list(named_params)
+    sets = {"params": [p.detach() for _, p in named_params],
+            "grads": [p.grad for _, p in named_params],
+            "masters": [opt.state.get(p, {}).get("master") for _, p in named_params]}
+    sets = {k: v for k, v in sets.items() if any(t is not None for t in v)}
+    cap = 1 << 16
+    while 4 * len(sets) * sum(min(p.numel(), cap) for _, p in named_params) > DUMP_SAMPLE_BYTES:
+        cap //= 2
+    picks = []
+    for i, (_, p) in enumerate(named_params):
+        n = p.numel()
+        if n <= cap:
+            picks.append(None)
+        else:
+            g = torch.Generator().manual_seed(1234 + i)
+            picks.append(torch.randperm(n, generator=g)[:cap].sort().values)
+    for name, tensors in sets.items():
+        parts = []
+        for t, idx in zip(tensors, picks):
+            if t is None:
+                continue
+            flat = t.detach().float().reshape(-1).cpu()
+            parts.append(flat if idx is None else flat[idx])
+        np.save(os.path.join(path, name + ".npy"), torch.cat(parts).numpy().astype(np.float32))
+    lg = logits.detach().float().cpu()
+    rows = max(1, DUMP_LOGITS_BYTES // (4 * max(1, lg[0].numel())))
+    if lg.shape[0] > rows:
+        g = torch.Generator().manual_seed(1234)
+        lg = lg[torch.randperm(lg.shape[0], generator=g)[:rows].sort().values]
+    np.save(os.path.join(path, "logits.npy"), lg.numpy().astype(np.float32))
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().reshape(1).numpy().astype(np.float32))
 
 
 def _dual_calls():
@@ -408,11 +505,14 @@ def main():
                             dtype=torch.bfloat16 if bf16 else torch.float32,
                             seed=1234, rank=rank, channels_last=not fp32_torch, device_step=a.graph == "on")
     nstep = [0]
+    last = {}
 
     def fwd_loss(x, y):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.precision == "autocast"):
             out = model(x)
             loss = cross_entropy(out, y)
+        if a.dump_outputs:
+            last["logits"] = out
         nstep[0] += 1
         if rank == a.fail_rank and nstep[0] == a.fail_step:
             print(f"rank {rank}: injected failure after the forward of step {nstep[0]}", file=sys.stderr, flush=True)
@@ -480,12 +580,14 @@ def main():
                                "hook_calls_per_step": gs.hook_calls / a.steps,
                                "step_ms_p50": r["step_ms"]["p50"]})
         best = min(sweep_rows, key=lambda x: x["ms_per_step"])
-        res = r  # telemetry / loss of the last cap's run; the line's value is the best cap's
+        res = r  # loss (and, with --full, telemetry) of the last cap's run; the line's value is the best cap's
     gsync = getattr(model, "sync", None)
     if gsync is not None:
         gsync.hook_s, gsync.hook_calls = 0.0, 0
     if not sweep:
         res = time_steps(run_step, a, dev, engine, graphed, c.backend, warmup=warm_left)
+    if a.dump_outputs and rank == 0:  # before anything below runs further steps
+        dump_outputs(a.dump_outputs, res["loss"], last["logits"], base.named_parameters(), opt)
     elapsed = res["elapsed"]
     comm_ms = res["comm_ms"] if not graphed else comm_ms_eager
     final_loss = float(res["loss"].detach().float())
@@ -551,8 +653,9 @@ def main():
                                      "not comparable unless model=googlenet and precision=fp32"},
             "step_ms": res["step_ms"],
             "warmup_step_ms": res["warm_ms"],
-            "telemetry": res["tele"],
         }
+        if a.full:
+            rec["telemetry"] = res["tele"]
         if sweep:
             rec["config"]["bucket_mb"] = best["bucket_mb"]
             rec["bucket_sweep"] = sweep_rows

@@ -8,7 +8,7 @@ set -uo pipefail
 N=${1:-1}; MODEL=${2:-resnet152}; BATCH=${3:-256}; shift 3 || true
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"; mkdir -p gpurun_out
-export HSA_ENABLE_IPC_MODE_LEGACY=0 MIOPEN_USER_DB_PATH=${MIOPEN_USER_DB_PATH:-$R/miopen_db}
+export HSA_ENABLE_IPC_MODE_LEGACY=0
 OUT=gpurun_out/bucket_sweep_${MODEL}_n${N}.jsonl
 : > "$OUT"
 for MB in 0 1 4 16 25 64 256; do

@@ -5,7 +5,6 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 mkdir -p gpurun_out
-export MIOPEN_USER_DB_PATH=$R/miopen_db
 TAG=${1:-round}
 timeout -k 10 600 python -m pytest tests -m gpu -q -x > gpurun_out/pytest_gpu.log 2>&1
 rc=$?

@@ -8,8 +8,8 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_gemm_stream.py tests/test_g
   --timeout 120 --timeout-method thread -p no:cacheprovider > $O/tests.log 2>&1 || { echo "tests failed"; tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 for i in 1 2 3; do
-  DLA_STREAM_ADD256=0 timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/off.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/on.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  DLA_STREAM_ADD256=0 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/off.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/on.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   echo "pair $i done"
 done
 python3 - <<'PY'

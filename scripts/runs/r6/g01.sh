@@ -34,5 +34,5 @@ done
 timeout -s KILL 120 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt1 -o k -- python3 $R/scripts/gemm_stall.py 250880 256 1024 fwd 6 > $O/kt.log 2>&1 || { tail -5 $O/kt.log; exit 1; }
 cp $(find /tmp/kt1 -name '*kernel_trace.csv' | head -1) $O/kt_fwd.csv
 cd $R
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.jsonl 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.jsonl 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python3 -c "import json;d=json.loads(open('$O/bench.jsonl').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d['telemetry']['before_timed'])"

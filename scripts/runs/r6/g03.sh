@@ -15,7 +15,7 @@ done
 cat $O/timing.txt
 for i in 1 2; do
   for d in 0 1; do
-    DLA_GEMM_DIRECT=$d timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$d.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_GEMM_DIRECT=$d timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$d.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

@@ -8,7 +8,7 @@ DLA_TILE256_MIN_K_STATS=256 timeout -k 10 600 python -u -m pytest tests/test_gpu
 tail -1 $O/test.txt
 for i in 1 2 3; do
   for k in 1024 256 512; do
-    DLA_TILE256_MIN_K_STATS=$k timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$k.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_TILE256_MIN_K_STATS=$k timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$k.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
   echo "round $i done"
 done

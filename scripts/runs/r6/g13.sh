@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_bn_act.py tests/test_gpu_be
 tail -1 $O/test2.txt
 for i in 1 2; do
   for d in 0 1; do
-    DLA_DEFER_APPLY=$d timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$d.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_DEFER_APPLY=$d timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$d.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
   echo "round $i done"
 done

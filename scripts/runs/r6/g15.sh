@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_gemm_apply.py -x -q --timeo
 tail -1 $O/test.txt
 for i in 1 2; do
   for k in 512 2048 1024; do
-    DLA_APPLY_MAX_K=$k timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$k.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_APPLY_MAX_K=$k timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$k.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
   echo "round $i done"
 done

@@ -6,9 +6,9 @@ set -o pipefail
 O=gpurun_out/r6/g16
 mkdir -p $O
 for i in 1 2 3; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/base.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
-  DLA_BN_EPILOGUE=stream timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/epi_stream.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
-  DLA_GEMM_DIRECT=1 timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/direct.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/base.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  DLA_BN_EPILOGUE=stream timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/epi_stream.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  DLA_GEMM_DIRECT=1 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/direct.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   echo "round $i done"
 done
 python3 - <<'PY'

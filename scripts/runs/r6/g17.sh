@@ -10,7 +10,7 @@ timeout -k 10 300 python scripts/wgrad_w4_ab.py > $O/timing.jsonl 2> $O/timing.e
 cat $O/timing.jsonl
 for i in 1 2; do
   for m in 0 1; do
-    DLA_WGRAD_W4=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$m.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_WGRAD_W4=$m timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$m.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

@@ -6,7 +6,7 @@ mkdir -p $O
 export MIOPEN_USER_DB_PATH=$(pwd)/miopen_db
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 "$@" > $O/$n.jsonl 2> $O/$n.err || { tail $O/$n.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 "$@" > $O/$n.jsonl 2> $O/$n.err || { tail $O/$n.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$O/$n.jsonl').read().strip().splitlines()[-1]); print('$n', d['value'], d['ms_per_step'], d['config'].get('global_batch'), d['telemetry']['before_timed']['gfxclk_mhz'])"
 }
 run resnet18_bs512 --model resnet18 --batch 512

@@ -7,7 +7,7 @@ mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_gpu_gemm_apply.py tests/test_gpu_dp.py -x -q --timeout 200 --timeout-method thread > $O/test.txt 2>&1 || { grep -E "Error|assert|FAIL" $O/test.txt | head -20; tail -30 $O/test.txt; exit 1; }
 tail -1 $O/test.txt
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/bench.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/bench.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
 done
 python3 -c "
 import json

@@ -6,7 +6,7 @@ O=gpurun_out/r6/g20
 mkdir -p $O
 for i in 1 2 3; do
   for m in 0 1; do
-    DLA_APPLY_SUBSAMPLE=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$m.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_APPLY_SUBSAMPLE=$m timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$m.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

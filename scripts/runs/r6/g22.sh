@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_gemm_stream.py tests/test_g
 tail -1 $O/test2.txt
 for i in 1 2 3; do
   for m in 0 1; do
-    DLA_DEFER_MID=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$m.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_DEFER_MID=$m timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$m.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

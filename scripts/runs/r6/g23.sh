@@ -5,7 +5,7 @@ O=gpurun_out/r6/g23
 mkdir -p $O
 run() {  # tag, env assignments...
   local t=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/$t.jsonl 2>> $O/err.log || { echo "$t failed"; tail $O/err.log; exit 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/$t.jsonl 2>> $O/err.log || { echo "$t failed"; tail $O/err.log; exit 1; }
 }
 for i in 1 2; do
   run base DLA_NOOP=1

@@ -18,7 +18,7 @@ done | tee $O/isolated.txt
 cd $R
 for i in 1 2 3; do
   for f in 0 1; do
-    DLA_HALO_FASTDIV=$f timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$f.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_HALO_FASTDIV=$f timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$f.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

@@ -9,7 +9,7 @@ tail -2 $O/full_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log | cut -c1-300
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 >> $O/bench.jsonl 2>> $O/bench.err || { tail $O/bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 >> $O/bench.jsonl 2>> $O/bench.err || { tail $O/bench.err; exit 1; }
 done
 python3 -c "
 import json
@@ -17,7 +17,7 @@ for l in open('$O/bench.jsonl'):
     if l.startswith('{'):
         d=json.loads(l); print(d['value'], d['ms_per_step'], d['telemetry']['before_timed'])"
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o trace -- python3 bench.py --steps 4 --warmup 3 > $O/prof.log 2>&1 || { tail $O/prof.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o trace -- python3 bench.py --full --steps 4 --warmup 3 > $O/prof.log 2>&1 || { tail $O/prof.log; exit 1; }
 python scripts/kernel_summary.py $O/prof/trace_results.db --steps 3 --out $O/ksum > /dev/null || exit 1
 rm -f $O/prof/trace_results.db
 head -45 $O/ksum.md

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_conv3x3.py -x -q -k "halo" 
 tail -1 $O/test.txt
 for i in 1 2 3; do
   for v in 0 1; do
-    DLA_HALO_DIRECT=$v timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$v.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_HALO_DIRECT=$v timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$v.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

@@ -7,8 +7,8 @@ mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_gpu_conv3x3.py -x -q -k "halo" --timeout 200 --timeout-method thread > $O/test.txt 2>&1 || { tail -30 $O/test.txt; exit 1; }
 tail -1 $O/test.txt
 for i in 1 2 3; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b0.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
-  DLA_HALO_V=1 DLA_HALO_DIRECT_FWD=1 timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b1.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b0.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+  DLA_HALO_V=1 DLA_HALO_DIRECT_FWD=1 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b1.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
 done
 python3 - <<'PY'
 import json

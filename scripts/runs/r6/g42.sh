@@ -5,7 +5,7 @@ O=gpurun_out/r6/g42
 mkdir -p $O
 for i in 1 2 3; do
   for k in 256 512 1024; do
-    DLA_TILE256_MIN_K_STATS=$k timeout -k 10 300 python bench.py --steps 20 --warmup 5 >> $O/b$k.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
+    DLA_TILE256_MIN_K_STATS=$k timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 >> $O/b$k.jsonl 2>> $O/err.log || { tail $O/err.log; exit 1; }
   done
 done
 python3 - <<'PY'

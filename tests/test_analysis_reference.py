@@ -1,14 +1,24 @@
-"""analysis.py on the reference's own raw CSVs (/root/reference/measurements), reproducing the
-published numbers exactly (collect_data.py:26-48,78-107).
-Skipped where the reference checkout is absent (e.g. on the GPU box)."""
+"""analysis.py on the reference's own raw CSVs, reproducing the published numbers exactly (SURVEY.md §6.1 /
+§6.3 / §6.4; collect_data.py:26-48,78-107). The ``*_times.csv`` files of the result folders used here are stored,
+with their folder layout, in tests/golden/reference_measurements.tar.gz."""
 import os
+import tarfile
 
 import pytest
 
 from distributed_learning_amd import analysis as A
 
-R = "/root/reference/measurements"
-pytestmark = pytest.mark.skipif(not os.path.isdir(R), reason="reference measurements not available")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_measurements.tar.gz")
+
+
+@pytest.fixture(scope="module")
+def R(tmp_path_factory):
+    d = tmp_path_factory.mktemp("reference_measurements")
+    with tarfile.open(GOLDEN) as t:
+        for m in t.getmembers():
+            assert m.isfile() and not os.path.isabs(m.name) and ".." not in m.name.split("/"), m.name
+        t.extractall(d)
+    return str(d)
 
 SINGLE = ["gpu2/results/experiment_single_1_33846316"]
 E1 = [f"gpu2/results/{f}" for f in ["experiment1_1_33847002", "experiment1_2_33846550", "experiment1_4_33846297",
@@ -28,14 +38,14 @@ PUBLISHED = {  # BASELINE.md headline table, img/s at 1 / 2 / 4 / 8 / 16 devices
 }
 
 
-def test_throughput_table_reproduces_published_numbers():
+def test_throughput_table_reproduces_published_numbers(R):
     data = A.with_ideal(A.load([os.path.join(R, f) for f in SINGLE + E1 + E2]))
     for exp, vals in PUBLISHED.items():
         for dev, want in zip([1, 2, 4, 8, 16], vals):
             assert round(data[(dev, exp)]["throughput"], 1) == want, (exp, dev)
 
 
-def test_phase_breakdown_single_and_ddp():
+def test_phase_breakdown_single_and_ddp(R):
     data = A.load([os.path.join(R, f) for f in SINGLE + E2])
     single = data[(1, "single")]
     want = {"get_data": 129.7, "data2dev": 9.4, "zero_grad": 5.5, "forward": 21.1, "backprop": 14.1, "sync": 0.0,
@@ -48,7 +58,7 @@ def test_phase_breakdown_single_and_ddp():
         assert round(data[(dev, "onestep_reduce")]["sync"], 1) == sync
 
 
-def test_fusion_sweep_reproduces_figure6():
+def test_fusion_sweep_reproduces_figure6(R):
     rows = A.fusion_sweep(os.path.join(R, "gpu1/results/fusion_experiment_ourdist_16_33723740"))
     got = {kib: (round(b, 1), round(s, 1)) for kib, b, s in rows}
     assert got == {1024: (1771.0, 1260.0), 4096: (1223.5, 738.4), 16384: (1196.4, 706.2), 65536: (1226.7, 914.2)}

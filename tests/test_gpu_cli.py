@@ -2,6 +2,7 @@
 experiment suites, the native engine + kernels, and the reference result artefacts
 (times.csv / loss.txt / config.txt, Appendix A), plus checkpoint / resume."""
 import os
+import shutil
 import subprocess
 import sys
 
@@ -16,7 +17,10 @@ pytestmark = pytest.mark.gpu
 def _run(tmp_path, model, experiment, *extra, batch=16, batches=3):
     from dist_util import free_port
 
-    env = dict(os.environ, PYTHONPATH=ROOT, MIOPEN_USER_DB_PATH=os.path.join(ROOT, "miopen_db"))
+    db = tmp_path / "miopen_db"  # MIOpen writes to its user database: start from a copy of the shipped one
+    if not db.exists():
+        shutil.copytree(os.path.join(ROOT, "miopen_db"), db)
+    env = dict(os.environ, PYTHONPATH=ROOT, MIOPEN_USER_DB_PATH=str(db))
     cmd = [sys.executable, "-m", "distributed_learning_amd.main", "1", "0", "1", "1", "127.0.0.1", "lo", model,
            "/nonexistent", "1", "--experiment", experiment, "--random_input", "1", "--limit_batches", str(batches),
            "--batch_size", str(batch), "--master_port", str(free_port()), "--results_root", str(tmp_path),
