@@ -61,6 +61,38 @@ void launch_pack(const PackEntry* entries, const int32_t* prefix, int ntensors, 
 void launch_unpack(const PackEntry* entries, const int32_t* prefix, int ntensors, int nblocks, int flat_dtype,
                    int dst_dtype, const void* flat, float scale, hipStream_t stream);
 
+// Fused LARS and tensor-list L2 norms (multi_tensor.hip): three kinds of launch per step, no host read.
+//   1. square sums: every block writes (sum p^2, sum g^2) of its chunk to partials[block_base + block]
+//      (plain stores, no atomics: bitwise reproducible);
+//   2. finalize (one block): per-tensor norms, the global gradient norm G, the clip factor, and
+//      local_lr[t] = lr_dev[group_t] * trust_t;
+//   3. update: d = c g + wd_t p; m = mu m + local_lr[t] d; p -= m (+ bf16 shadow).
+// Static per-tensor row of the device table: depends only on the tensors taking part, their sizes
+// and their group's hyper-parameters.
+struct LarsTensor {
+  int32_t part_begin, part_end;  // this tensor's range of per-block partials
+  int32_t group;                 // index into lr_dev
+  int32_t adapt;                 // 0: excluded from layer-wise scaling (trust 1, no weight decay)
+  float weight_decay;            // wd_t: already 0 for an excluded tensor
+  float eta, eps, momentum;
+};
+struct LarsList {
+  SgdList l;        // param may be null for the square-sum pass (norms of the grad slot only)
+  int tensor_base;  // table row of l.e[0]
+  int block_base;   // partial slot of this launch's block 0
+};
+// fp32 workspace: [0] c = grad_scale * clip, [1] G, [2] clip, [3] spare | local_lr[T] |
+// (||p_t||, ||g_t||)[T] | partials (sum p^2, sum g^2)[nblocks], 8-byte aligned
+constexpr int kLarsHead = 4;
+constexpr int64_t lars_partials_offset(int ntensors) { return (kLarsHead + 3 * (int64_t)ntensors + 1) & ~(int64_t)1; }
+inline int64_t lars_ws_floats(int ntensors, int nblocks) { return lars_partials_offset(ntensors) + 2 * (int64_t)nblocks; }
+void launch_sqsum_list(const LarsList& list, int nblocks, int grad_dtype, float* ws, int ntensors, hipStream_t stream);
+// lr_dev may be null (norms only: local_lr[t] = trust_t)
+void launch_lars_finalize(const LarsTensor* table, int ntensors, const float* lr_dev, float grad_scale,
+                          float max_grad_norm, float* ws, hipStream_t stream);
+void launch_lars_list(const LarsList& list, int nblocks, int grad_dtype, const LarsTensor* table, const float* ws,
+                      hipStream_t stream);
+
 // ---- elementwise reductions for the collectives (reduce.hip) --------------------------------
 constexpr int kMaxReduceSrc = 8;
 struct ReduceSrcs {

@@ -56,28 +56,16 @@ __global__ __launch_bounds__(kMTBlock) void sgd_list_kernel(SgdList list, SgdPar
   sgd_body<G, kMomentum>(list.e[t], (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk, hp);
 }
 
-template <typename G, bool kMomentum>
-__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp) {
+// One chunk of one tensor through `update(p, g, m, p_out, m_out)`: reads p, g (fp32 or bf16) and m,
+// writes p, m and the optional bf16 shadow. Shared by the SGD and LARS update kernels.
+template <typename G, bool kMomentum, typename F>
+__device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, F update) {
   const int64_t n = e.numel;
   const int64_t end = min(n, chunk0 + (int64_t)kMTChunk);
   float* __restrict__ p = e.param;
   const G* __restrict__ g = reinterpret_cast<const G*>(e.grad);
   float* __restrict__ m = e.momentum;
   bf16_t* __restrict__ pb = e.param_bf16;
-  const float lr = hp.lr, mu = hp.momentum, damp1 = 1.f - hp.dampening, wd = hp.weight_decay;
-  const float gs = hp.grad_scale;
-  const bool first = hp.first_step != 0;
-  const bool nest = hp.nesterov != 0;
-
-  auto update = [&](float pv, float gv, float mv, float& po, float& mo) {
-    float d = gv * gs;
-    if (wd != 0.f) d = fmaf(wd, pv, d);
-    if (kMomentum) {
-      mo = first ? d : fmaf(mu, mv, damp1 * d);
-      d = nest ? fmaf(mu, mo, d) : mo;
-    }
-    po = fmaf(-lr, d, pv);
-  };
 
   const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
                          (kMomentum ? reinterpret_cast<uintptr_t>(m) : 0) |
@@ -119,6 +107,23 @@ __device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, cons
       if (pb) pb[i] = f32_to_bf16(po);
     }
   }
+}
+
+template <typename G, bool kMomentum>
+__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp) {
+  const float lr = hp.lr, mu = hp.momentum, damp1 = 1.f - hp.dampening, wd = hp.weight_decay;
+  const float gs = hp.grad_scale;
+  const bool first = hp.first_step != 0;
+  const bool nest = hp.nesterov != 0;
+  update_chunk<G, kMomentum>(e, chunk0, [&](float pv, float gv, float mv, float& po, float& mo) {
+    float d = gv * gs;
+    if (wd != 0.f) d = fmaf(wd, pv, d);
+    if (kMomentum) {
+      mo = first ? d : fmaf(mu, mv, damp1 * d);
+      d = nest ? fmaf(mu, mo, d) : mo;
+    }
+    po = fmaf(-lr, d, pv);
+  });
 }
 
 // --------------------------------------------------------------------------------------------
@@ -265,6 +270,178 @@ void launch_unpack(const PackEntry* entries, const int32_t* prefix, int ntensors
     hipLaunchKernelGGL((unpack_kernel<bf16_t, bf16_t>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
   else
     hipLaunchKernelGGL((unpack_kernel<float, bf16_t>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
+}
+
+// --------------------------------------------------------------------------------------------
+// Fused LARS (You et al. 2017) and tensor-list L2 norms; layout and formula in dla_kernels.h.
+// HBM-bound like SGD: the square-sum pass adds one read of p and g to the update's traffic.
+// --------------------------------------------------------------------------------------------
+// Square sums of one chunk: 16 elements per thread accumulated in fp32 in a fixed order, then the
+// wave butterfly, then the 4 waves through LDS. One plain 8-byte store per block.
+template <typename G>
+__global__ __launch_bounds__(kMTBlock) void sqsum_list_kernel(LarsList list, float* __restrict__ partials) {
+  const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
+  const SgdEntry& e = list.l.e[t];
+  const int64_t chunk0 = (int64_t)(blockIdx.x - list.l.prefix[t]) * kMTChunk;
+  const int64_t end = min(e.numel, chunk0 + (int64_t)kMTChunk);
+  const float* __restrict__ p = e.param;
+  const G* __restrict__ g = reinterpret_cast<const G*>(e.grad);
+  float sp = 0.f, sg = 0.f;
+  const bool aligned = (((p ? reinterpret_cast<uintptr_t>(p) : 0) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+  if (aligned && end - chunk0 == kMTChunk) {
+#pragma unroll
+    for (int k = 0; k < kMTPerThread / 4; ++k) {
+      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
+      float4_t gv;
+      if constexpr (sizeof(G) == 4) {
+        gv = *reinterpret_cast<const float4_t*>(reinterpret_cast<const float*>(g) + i);
+      } else {
+        ushort4_t gr = *reinterpret_cast<const ushort4_t*>(reinterpret_cast<const bf16_t*>(g) + i);
+        gv = float4_t{bf16_to_f32(gr.x), bf16_to_f32(gr.y), bf16_to_f32(gr.z), bf16_to_f32(gr.w)};
+      }
+      const float4_t pv = p ? *reinterpret_cast<const float4_t*>(p + i) : float4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sg = fmaf(gv[j], gv[j], sg);
+        sp = fmaf(pv[j], pv[j], sp);
+      }
+    }
+  } else {
+    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
+      const float gv = Cvt<G>::to_f32(g[i]);
+      sg = fmaf(gv, gv, sg);
+      if (p) sp = fmaf(p[i], p[i], sp);
+    }
+  }
+  sp = wave_sum(sp);
+  sg = wave_sum(sg);
+  __shared__ float sm[2][kMTBlock / kWave];
+  const int wave = threadIdx.x / kWave;
+  if (threadIdx.x % kWave == 0) {
+    sm[0][wave] = sp;
+    sm[1][wave] = sg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = sm[0][0], b = sm[1][0];
+#pragma unroll
+    for (int w = 1; w < kMTBlock / kWave; ++w) {
+      a += sm[0][w];
+      b += sm[1][w];
+    }
+    float* out = partials + 2 * ((int64_t)list.block_base + blockIdx.x);
+    out[0] = a;
+    out[1] = b;
+  }
+}
+
+// One block of 16 waves. Wave w sums the partial ranges of tensors w, w + 16, ... (lane-strided, then
+// the wave butterfly: a fixed order) and keeps their squared sums in the norms slots; the waves'
+// gradient totals meet in LDS. Then every thread turns squared sums into norms, trust ratios and
+// local rates. The block is latency-bound (a table row, then its partials, per tensor), so it has 16
+// waves and fetches the next row ahead: on ResNet-50's 161 tensors a 4-wave block without the
+// prefetch took 42 us, a third of the whole SGD step (both forms timed in profiles/lars/README.md).
+constexpr int kFinBlock = 1024;
+constexpr int kFinWaves = kFinBlock / kWave;
+
+__global__ __launch_bounds__(kFinBlock) void lars_finalize_kernel(const LarsTensor* __restrict__ table, int ntensors,
+                                                                  const float* __restrict__ lr_dev, float grad_scale,
+                                                                  float max_grad_norm, float* ws) {
+  float* local_lr = ws + kLarsHead;
+  float* norms = local_lr + ntensors;
+  const float2* partials = reinterpret_cast<const float2*>(ws + lars_partials_offset(ntensors));
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  float total = 0.f;
+  int nb = 0, ne = 0;
+  if (wave < ntensors) {
+    nb = table[wave].part_begin;
+    ne = table[wave].part_end;
+  }
+  for (int t = wave; t < ntensors; t += kFinWaves) {
+    const int b = nb, e = ne;
+    if (t + kFinWaves < ntensors) {
+      nb = table[t + kFinWaves].part_begin;
+      ne = table[t + kFinWaves].part_end;
+    }
+    float sp = 0.f, sg = 0.f;
+    for (int i = b + lane; i < e; i += kWave) {
+      const float2 v = partials[i];
+      sp += v.x;
+      sg += v.y;
+    }
+    sp = wave_sum(sp);
+    sg = wave_sum(sg);
+    total += sg;
+    if (lane == 0) {
+      norms[2 * t] = sp;
+      norms[2 * t + 1] = sg;
+    }
+  }
+  __shared__ float sm[kFinWaves];
+  if (lane == 0) sm[wave] = total;
+  __syncthreads();  // also orders the squared sums stored above before the loads below
+  total = sm[0];
+#pragma unroll
+  for (int w = 1; w < kFinWaves; ++w) total += sm[w];
+  const float gnorm = grad_scale * sqrtf(total);
+  const float clip = max_grad_norm > 0.f ? fminf(1.f, max_grad_norm / (gnorm + 1e-6f)) : 1.f;
+  const float c = grad_scale * clip;
+  if (threadIdx.x == 0) {
+    ws[0] = c;
+    ws[1] = gnorm;
+    ws[2] = clip;
+    ws[3] = 0.f;
+  }
+  for (int t = threadIdx.x; t < ntensors; t += kFinBlock) {
+    const LarsTensor r = table[t];
+    const float wn = sqrtf(norms[2 * t]), gr = sqrtf(norms[2 * t + 1]);
+    const float gn = c * gr;
+    float trust = 1.f;
+    if (r.adapt && wn > 0.f && gn > 0.f) trust = r.eta * wn / (gn + r.weight_decay * wn + r.eps);
+    local_lr[t] = lr_dev ? lr_dev[r.group] * trust : trust;
+    norms[2 * t] = wn;
+    norms[2 * t + 1] = gr;
+  }
+}
+
+template <typename G>
+__global__ __launch_bounds__(kMTBlock) void lars_list_kernel(LarsList list, const LarsTensor* __restrict__ table,
+                                                             const float* __restrict__ ws) {
+  const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
+  const int row = list.tensor_base + t;
+  const float c = ws[0], llr = ws[kLarsHead + row];
+  const float wd = table[row].weight_decay, mu = table[row].momentum;
+  update_chunk<G, true>(list.l.e[t], (int64_t)(blockIdx.x - list.l.prefix[t]) * kMTChunk,
+                        [&](float pv, float gv, float mv, float& po, float& mo) {
+                          float d = gv * c;
+                          if (wd != 0.f) d = fmaf(wd, pv, d);
+                          mo = fmaf(mu, mv, llr * d);
+                          po = pv - mo;
+                        });
+}
+
+void launch_sqsum_list(const LarsList& list, int nblocks, int grad_dtype, float* ws, int ntensors,
+                       hipStream_t stream) {
+  if (nblocks <= 0 || list.l.ntensors <= 0) return;
+  dim3 grid(nblocks), block(kMTBlock);
+  float* partials = ws + lars_partials_offset(ntensors);
+  if (grad_dtype == kF32) hipLaunchKernelGGL((sqsum_list_kernel<float>), grid, block, 0, stream, list, partials);
+  else hipLaunchKernelGGL((sqsum_list_kernel<bf16_t>), grid, block, 0, stream, list, partials);
+}
+
+void launch_lars_finalize(const LarsTensor* table, int ntensors, const float* lr_dev, float grad_scale,
+                          float max_grad_norm, float* ws, hipStream_t stream) {
+  if (ntensors <= 0) return;
+  hipLaunchKernelGGL(lars_finalize_kernel, dim3(1), dim3(kFinBlock), 0, stream, table, ntensors, lr_dev, grad_scale,
+                     max_grad_norm, ws);
+}
+
+void launch_lars_list(const LarsList& list, int nblocks, int grad_dtype, const LarsTensor* table, const float* ws,
+                      hipStream_t stream) {
+  if (nblocks <= 0 || list.l.ntensors <= 0) return;
+  dim3 grid(nblocks), block(kMTBlock);
+  if (grad_dtype == kF32) hipLaunchKernelGGL((lars_list_kernel<float>), grid, block, 0, stream, list, table, ws);
+  else hipLaunchKernelGGL((lars_list_kernel<bf16_t>), grid, block, 0, stream, list, table, ws);
 }
 
 }  // namespace dla

@@ -159,6 +159,170 @@ void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
   flush();
 }
 
+// ------------------------------------------------------------------------------------------
+// Fused LARS / tensor-list L2 norms. LarsPlan owns what is static for one set of participating
+// tensors: the device table (partial ranges, group, hyper-parameters) and the workspace. A step
+// is square-sum launches, one finalize, update launches; nothing is read back to the host.
+// ------------------------------------------------------------------------------------------
+class LarsPlan {
+ public:
+  LarsPlan(std::vector<int64_t> numels, std::vector<int64_t> groups, std::vector<bool> adapt,
+           std::vector<double> weight_decay, std::vector<double> eta, std::vector<double> eps,
+           std::vector<double> momentum, c10::optional<at::Tensor> lr_dev, at::Tensor like)
+      : numels_(std::move(numels)) {
+    const size_t T = numels_.size();
+    TORCH_CHECK(T > 0 && T < (size_t)1 << 24, "LarsPlan: bad tensor count ", T);
+    TORCH_CHECK(groups.size() == T && adapt.size() == T && weight_decay.size() == T && eta.size() == T &&
+                    eps.size() == T && momentum.size() == T,
+                "LarsPlan: per-tensor lists must have one entry per tensor");
+    TORCH_CHECK(like.is_cuda(), "LarsPlan: GPU tensors only");
+    int64_t ngroups = 1;
+    if (lr_dev.has_value() && lr_dev->defined()) {
+      check_dev(*lr_dev, "lr_dev");
+      TORCH_CHECK(lr_dev->scalar_type() == at::kFloat && lr_dev->device() == like.device() && lr_dev->is_contiguous(),
+                  "LarsPlan: lr_dev must be a contiguous fp32 tensor on the parameters' device");
+      lr_dev_ = *lr_dev;
+      ngroups = lr_dev_.numel();
+    }
+    const int chunk = mt_chunk_elems();
+    std::vector<LarsTensor> rows(T);
+    int64_t blocks = 0;
+    for (size_t i = 0; i < T; ++i) {
+      TORCH_CHECK(numels_[i] >= 0, "LarsPlan: negative numel");
+      TORCH_CHECK(groups[i] >= 0 && groups[i] < ngroups, "LarsPlan: group ", groups[i], " out of range");
+      LarsTensor& r = rows[i];
+      r.part_begin = (int32_t)blocks;
+      blocks += (numels_[i] + chunk - 1) / chunk;
+      TORCH_CHECK(blocks < ((int64_t)1 << 30), "LarsPlan: too many chunks");
+      r.part_end = (int32_t)blocks;
+      r.group = (int32_t)groups[i];
+      r.adapt = adapt[i] ? 1 : 0;
+      r.weight_decay = adapt[i] ? (float)weight_decay[i] : 0.f;
+      r.eta = (float)eta[i];
+      r.eps = (float)eps[i];
+      r.momentum = (float)momentum[i];
+    }
+    nblocks_ = (int)blocks;
+    table_ = upload(rows.data(), rows.size() * sizeof(LarsTensor), like.device());
+    ws_ = at::empty({lars_ws_floats((int)T, nblocks_)}, like.options().dtype(at::kFloat));
+  }
+
+  int ntensors() const { return (int)numels_.size(); }
+  const LarsTensor* table() const { return reinterpret_cast<const LarsTensor*>(table_.data_ptr()); }
+  float* ws() const { return ws_.data_ptr<float>(); }
+  at::Tensor grad_norm() const { return ws_.narrow(0, 1, 1); }
+  at::Tensor local_lr() const { return ws_.narrow(0, kLarsHead, ntensors()); }
+  // [T, 2]: (||p_t||, ||g_t||), the gradient norm before grad_scale and clipping
+  at::Tensor norms() const { return ws_.narrow(0, kLarsHead + ntensors(), 2 * (int64_t)ntensors()).view({-1, 2}); }
+
+  // params may be empty (norms of `grads` only); moms / shadows are used by the update pass alone.
+  void run(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+           const std::vector<at::Tensor>& moms, const std::vector<c10::optional<at::Tensor>>& shadows, bool update,
+           double grad_scale, double max_grad_norm) {
+    const size_t T = numels_.size();
+    TORCH_CHECK(grads.size() == T, "lars: the plan was built for ", T, " tensors, got ", grads.size());
+    TORCH_CHECK(params.empty() || params.size() == T, "lars: params/grads size mismatch");
+    TORCH_CHECK(!update || (params.size() == T && moms.size() == T && lr_dev_.defined()),
+                "lars: the update needs a parameter and a momentum buffer per gradient, and lr_dev");
+    TORCH_CHECK(shadows.empty() || shadows.size() == T, "lars: shadow list size mismatch");
+    const int chunk = mt_chunk_elems();
+    // the launches of both passes, built once: by-value lists split at kMaxList tensors and at grad dtype changes
+    struct Launch {
+      LarsList list;
+      int blocks, gdt;
+    };
+    std::vector<Launch> launches;
+    Launch cur{};
+    int block_base = 0;
+    auto flush = [&](int next_row) {
+      if (cur.list.l.ntensors > 0) {
+        cur.list.l.prefix[cur.list.l.ntensors] = cur.blocks;
+        launches.push_back(cur);
+        block_base += cur.blocks;
+      }
+      cur = Launch{};
+      cur.list.tensor_base = next_row;
+      cur.list.block_base = block_base;
+    };
+    flush(0);
+    for (size_t i = 0; i < T; ++i) {
+      const at::Tensor& g = grads[i];
+      check_dev(g, "grad");
+      TORCH_CHECK(g.device() == ws_.device(), "lars: tensor ", i, " is on another device than the plan");
+      TORCH_CHECK(g.numel() == numels_[i], "lars: tensor ", i, " has ", g.numel(), " elements, the plan ", numels_[i]);
+      const int gdt = dtype_code(g);
+      if (cur.list.l.ntensors > 0 && gdt != cur.gdt) flush((int)i);
+      cur.gdt = gdt;
+      SgdEntry e{};
+      e.grad = g.data_ptr();
+      e.numel = g.numel();
+      if (!params.empty()) {
+        const at::Tensor& p = params[i];
+        check_dev(p, "param");
+        TORCH_CHECK(p.scalar_type() == at::kFloat && p.device() == g.device(),
+                    "lars: parameters/masters must be fp32 on the gradients' device");
+        TORCH_CHECK(same_layout(g, p), "lars: grad ", i, " must match its parameter's layout");
+        e.param = p.data_ptr<float>();
+      }
+      if (update) {
+        const at::Tensor& m = moms[i];
+        check_dev(m, "momentum");
+        TORCH_CHECK(m.scalar_type() == at::kFloat && m.device() == g.device() && same_layout(m, params[i]),
+                    "lars: bad momentum buffer");
+        e.momentum = m.data_ptr<float>();
+        if (!shadows.empty() && shadows[i].has_value() && (*shadows[i]).defined()) {
+          const at::Tensor& s = *shadows[i];
+          check_dev(s, "bf16 shadow");
+          TORCH_CHECK(s.scalar_type() == at::kBFloat16 && s.device() == g.device() && same_layout(s, params[i]),
+                      "lars: bad shadow");
+          e.param_bf16 = reinterpret_cast<uint16_t*>(s.data_ptr());
+        }
+      }
+      cur.list.l.prefix[cur.list.l.ntensors] = cur.blocks;
+      cur.list.l.e[cur.list.l.ntensors++] = e;
+      cur.blocks += (int)((e.numel + chunk - 1) / chunk);
+      if (cur.list.l.ntensors == kMaxList) flush((int)i + 1);
+    }
+    flush((int)T);
+    TORCH_CHECK(block_base == nblocks_, "lars: chunk count changed since the plan was built");
+    hipStream_t st = current_stream(ws_);
+    for (const Launch& L : launches) launch_sqsum_list(L.list, L.blocks, L.gdt, ws(), (int)T, st);
+    launch_lars_finalize(table(), (int)T, lr_dev_.defined() ? lr_dev_.data_ptr<float>() : nullptr, (float)grad_scale,
+                         (float)max_grad_norm, ws(), st);
+    if (update)
+      for (const Launch& L : launches) launch_lars_list(L.list, L.blocks, L.gdt, table(), ws(), st);
+    launches_ = (int)launches.size() * (update ? 2 : 1) + 1;
+  }
+
+  int last_launches() const { return launches_; }
+
+ private:
+  std::vector<int64_t> numels_;
+  at::Tensor table_, ws_, lr_dev_;
+  int nblocks_ = 0, launches_ = 0;
+};
+
+void lars_step_list(LarsPlan& plan, std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                    std::vector<at::Tensor> moms, std::vector<c10::optional<at::Tensor>> shadows, double grad_scale,
+                    double max_grad_norm) {
+  plan.run(params, grads, moms, shadows, true, grad_scale, max_grad_norm);
+}
+
+// (per_tensor[T], total[1]) = scale * (||t||_2 of each tensor, of all of them together), fp32.
+// A one-off plan per call: a host-built table uploaded synchronously and a fresh workspace that the
+// results are views of -- not for the inside of a step or a graph capture (FusedLARS caches its plan).
+std::vector<at::Tensor> multi_tensor_l2norm(std::vector<at::Tensor> tensors, double scale) {
+  TORCH_CHECK(!tensors.empty(), "multi_tensor_l2norm: empty tensor list");
+  const size_t T = tensors.size();
+  std::vector<int64_t> numels(T);
+  for (size_t i = 0; i < T; ++i) numels[i] = tensors[i].numel();
+  LarsPlan plan(numels, std::vector<int64_t>(T, 0), std::vector<bool>(T, false), std::vector<double>(T, 0.0),
+                std::vector<double>(T, 0.0), std::vector<double>(T, 0.0), std::vector<double>(T, 0.0), c10::nullopt,
+                tensors[0]);
+  plan.run({}, tensors, {}, {}, false, scale, 0.0);
+  return {plan.norms().select(1, 1).mul(scale), plan.grad_norm()};
+}
+
 void pack_tensors_on(const std::vector<at::Tensor>& ts, const std::vector<int64_t>& offs, const at::Tensor& flat,
                      float scale, hipStream_t st) {
   TORCH_CHECK(ts.size() == offs.size(), "pack: tensors/offsets size mismatch");
@@ -278,6 +442,17 @@ void bind_ops(pybind11::module& m) {
       .def("total_numel", &PackTable::total_numel);
   m.def("reduce_sum_", &reduce_sum_, "dst = scale*([dst] + sum(srcs))");
   m.def("sgd_step_list", &sgd_step_list, "fused SGD over a by-value tensor list (<= 32 tensors per launch)");
+  pybind11::class_<LarsPlan>(m, "LarsPlan")
+      .def(pybind11::init<std::vector<int64_t>, std::vector<int64_t>, std::vector<bool>, std::vector<double>,
+                          std::vector<double>, std::vector<double>, std::vector<double>, c10::optional<at::Tensor>,
+                          at::Tensor>())
+      .def("grad_norm", &LarsPlan::grad_norm)
+      .def("local_lr", &LarsPlan::local_lr)
+      .def("norms", &LarsPlan::norms)
+      .def("last_launches", &LarsPlan::last_launches);
+  m.def("lars_step_list", &lars_step_list,
+        "fused LARS over by-value tensor lists: square sums, finalize (norms, clip, trust), update");
+  m.def("multi_tensor_l2norm", &multi_tensor_l2norm, "(per-tensor, total) L2 norms of a tensor list times scale");
   m.def("pack_list", &pack_list, "gather tensors into a flat buffer at element offsets (by-value list launch)");
   m.def("scale_", &scale_, "t *= scale");
   m.def("uniform_", &uniform_, "Philox uniform fill (stream position offset [+ *step * per_step])",

@@ -52,6 +52,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--momentum", type=float, default=0.5)
     p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                   help="sgd: fused momentum SGD (the reference's); lars: fused layer-wise adaptive rate scaling "
+                        "for large global batches")
+    p.add_argument("--lars_eta", type=float, default=1e-3, help="LARS trust coefficient")
+    p.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip gradients by their global L2 norm (0 = off; --optimizer lars only)")
+    p.add_argument("--warmup_steps", type=int, default=0, help="linear learning-rate warmup from 0 over this many batches")
+    p.add_argument("--total_steps", type=int, default=0,
+                   help="polynomial learning-rate decay to 0 at this batch (0 = no decay)")
+    p.add_argument("--lr_power", type=float, default=2.0, help="power of the polynomial decay")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--master_port", type=int, default=29501)
     # MI355X options
@@ -86,7 +96,14 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv: Optional[List[str]] = None):
-    config = build_parser().parse_args(argv)
+    parser = build_parser()
+    config = parser.parse_args(argv)
+    if config.max_grad_norm < 0:
+        parser.error("--max_grad_norm must be >= 0")
+    if config.max_grad_norm > 0 and config.optimizer != "lars":
+        parser.error("--max_grad_norm needs --optimizer lars (the fused SGD does not clip)")
+    if config.warmup_steps < 0 or config.total_steps < 0:
+        parser.error("--warmup_steps and --total_steps must be >= 0")
     return finalize(config)
 
 

@@ -1,2 +1,3 @@
 """Native (HIP/gfx950) ops and their PyTorch reference fallbacks."""
 from . import nn  # noqa: F401
+from .optim import multi_tensor_l2norm  # noqa: F401

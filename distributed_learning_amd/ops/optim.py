@@ -9,6 +9,11 @@ On MI355X the update is HBM-bound (fp32: read p, g, m; write p, m = 20 B/param; 
 Extras over torch.optim.SGD: ``grad_scale`` (fold 1/N or loss-scale into the update) and an
 optional bf16 shadow copy of each parameter written in the same pass.
 On CPU (or without the extension) it falls back to the exact ``torch.optim.SGD`` math.
+
+FusedLARS: layer-wise adaptive rate scaling (You et al. 2017) for the large-batch configurations,
+with the norms, trust ratios and the global-norm clip computed on the device: a step is a handful
+of launches, reads nothing back to the host, and takes its learning rate from device memory so a
+captured step follows a schedule (``set_lr``). ``poly_warmup_lr`` is the usual schedule for it.
 """
 from __future__ import annotations
 
@@ -19,25 +24,11 @@ import torch
 from . import _ext
 
 
-class FusedSGD(torch.optim.Optimizer):
-    """SGD(momentum, dampening, nesterov, weight_decay) as one native launch per (grad dtype) group.
+class _MasterWeightsOptimizer(torch.optim.Optimizer):
+    """What FusedSGD and FusedLARS share: fp32 master copies of low-precision parameters and a
+    ``load_state_dict`` that keeps them (and the momentum buffers) fp32."""
 
-    ``master_weights=True``: low-precision (bf16) parameters get an fp32 master copy in the
-    optimizer state; the kernel reads the bf16 gradient, updates master + momentum in fp32 and
-    writes the rounded bf16 parameter back in the same pass (no separate cast kernels, and no
-    autocast weight casts in the forward). fp32 parameters (e.g. BatchNorm) are updated in place.
-    """
-
-    def __init__(self, params, lr: float = 0.01, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, grad_scale: float = 1.0,
-                 master_weights: bool = False):
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                        nesterov=nesterov, grad_scale=grad_scale)
-        super().__init__(params, defaults)
-        self.master_weights = master_weights
-        self._tables = {}
+    master_weights = False
 
     def load_state_dict(self, state_dict):
         """torch.optim.Optimizer.load_state_dict casts floating-point state to each parameter's dtype
@@ -62,6 +53,27 @@ class FusedSGD(torch.optim.Optimizer):
         if "master" not in st:
             st["master"] = torch.empty_like(p, dtype=torch.float32).copy_(p)
         return st["master"]
+
+
+class FusedSGD(_MasterWeightsOptimizer):
+    """SGD(momentum, dampening, nesterov, weight_decay) as one native launch per (grad dtype) group.
+
+    ``master_weights=True``: low-precision (bf16) parameters get an fp32 master copy in the
+    optimizer state; the kernel reads the bf16 gradient, updates master + momentum in fp32 and
+    writes the rounded bf16 parameter back in the same pass (no separate cast kernels, and no
+    autocast weight casts in the forward). fp32 parameters (e.g. BatchNorm) are updated in place.
+    """
+
+    def __init__(self, params, lr: float = 0.01, momentum: float = 0.0, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False, grad_scale: float = 1.0,
+                 master_weights: bool = False):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                        nesterov=nesterov, grad_scale=grad_scale)
+        super().__init__(params, defaults)
+        self.master_weights = master_weights
+        self._tables = {}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -130,3 +142,207 @@ class FusedSGD(torch.optim.Optimizer):
                     b.mul_(mom).add_(d, alpha=1 - damp)
                 d = d.add(b, alpha=mom) if nest else b
             p.add_(d, alpha=-lr)
+
+
+def poly_warmup_lr(step: int, base_lr: float, warmup_steps: int, total_steps: int, power: float = 2.0,
+                   end_lr: float = 0.0) -> float:
+    """Linear from 0 to ``base_lr`` over ``warmup_steps``, then polynomial decay to ``end_lr`` at
+    ``total_steps`` (and ``end_lr`` after it). Without a decay phase (``total_steps <= warmup_steps``)
+    the rate stays at ``base_lr`` after the warmup; with both 0 it is constant."""
+    if step < warmup_steps:
+        return base_lr * step / warmup_steps
+    if total_steps <= warmup_steps:
+        return base_lr
+    frac = min(1.0, (step - warmup_steps) / (total_steps - warmup_steps))
+    return end_lr + (base_lr - end_lr) * (1.0 - frac) ** power
+
+
+def multi_tensor_l2norm(tensors, scale: float = 1.0):
+    """``(per_tensor[T], total[1])``: ``scale * ||t||_2`` of every tensor of the list and of all of
+    them together, fp32. GPU lists (fp32 / bf16, dense) go through the square-sum and finalize
+    kernels of the fused LARS; CPU lists through torch.
+
+    The norms are never read back to the host, but every call builds its table of partial ranges on
+    the host and uploads it (a synchronous copy) and allocates a fresh workspace that the results
+    are views of: a utility for logging and tests, not for the inside of a step or of a graph
+    capture. ``FusedLARS`` keeps its table and workspace across steps and has neither cost."""
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("multi_tensor_l2norm: empty tensor list")
+    if tensors[0].is_cuda and (_ext.available() or _ext.gpu_required()):
+        per, total = _ext.require().multi_tensor_l2norm(tensors, float(scale))
+        return per, total
+    per = torch.stack([torch.linalg.vector_norm(t.detach().float()) for t in tensors])
+    return per * scale, (torch.linalg.vector_norm(per) * scale).reshape(1)
+
+
+class FusedLARS(_MasterWeightsOptimizer):
+    """Momentum SGD with layer-wise adaptive rate scaling and optional clipping by the global
+    gradient norm. Per tensor ``t`` (``s`` = ``grad_scale``, sums over every tensor stepped in this call)::
+
+        G     = s * sqrt(sum_t ||g_t||^2)
+        clip  = min(1, max_grad_norm / (G + 1e-6))          (1 when max_grad_norm == 0)
+        c     = s * clip
+        wn, gn = ||p_t||, c * ||g_t||
+        trust = eta * wn / (gn + wd * wn + eps)              (1 when excluded, or wn == 0, or gn == 0)
+        m     = momentum * m + lr * trust * (c * g + wd * p)
+        p     = p - m
+
+    With ``exclude_bias_and_norm`` tensors of ``ndim <= 1`` (biases, BatchNorm scale and shift) are
+    excluded: trust 1 and no weight decay. No Nesterov, no dampening.
+
+    On the GPU a step is square-sum launches, one finalize launch and update launches over by-value
+    tensor lists (csrc/kernels/multi_tensor.hip), whatever the number of param groups. The learning
+    rate of each group lives in a device array that the finalize reads, so a step captured in a HIP
+    graph follows ``set_lr`` calls made between replays. On CPU, or for low-precision parameters
+    without masters, the same formula runs in torch (also without a host read).
+    """
+
+    _MAX_PLANS = 4  # cached native plans (sets of participating tensors), least recently used out first
+
+    def __init__(self, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0, eta: float = 1e-3,
+                 eps: float = 0.0, exclude_bias_and_norm: bool = True, grad_scale: float = 1.0,
+                 max_grad_norm: float = 0.0, master_weights: bool = False):
+        if lr < 0 or momentum < 0 or weight_decay < 0 or eta <= 0 or eps < 0 or max_grad_norm < 0:
+            raise ValueError("FusedLARS: lr, momentum, weight_decay, eps, max_grad_norm >= 0 and eta > 0 required")
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=eta, eps=eps,
+                        exclude_bias_and_norm=exclude_bias_and_norm)
+        super().__init__(params, defaults)
+        self.grad_scale = grad_scale
+        self.max_grad_norm = max_grad_norm
+        self.master_weights = master_weights
+        self.last_grad_norm: Optional[torch.Tensor] = None  # device tensor [1]: G of the last step
+        self._tables = {}     # participating tensors + hyper-parameters -> native plan (table, workspace)
+        self._captured = []   # plans a HIP graph was captured with, kept alive outside the cache
+        self._lr_dev = None   # fp32 [len(param_groups)] on the parameters' device
+        self._lr_seen: List[Optional[float]] = []
+        self.last_launches = 0
+
+    # -- learning rate -----------------------------------------------------------------------------
+    def set_lr(self, lr: float, group: Optional[int] = None) -> None:
+        """Set the learning rate of one param group (all when ``group`` is None): ``param_groups`` and
+        the device scalar the kernels read. A stream-ordered fill, legal between graph replays."""
+        for gi, g in enumerate(self.param_groups):
+            if group is None or gi == group:
+                g["lr"] = lr
+                if self._lr_dev is not None:
+                    self._lr_dev[gi].fill_(lr)
+                    self._lr_seen[gi] = lr
+
+    def _sync_lr(self, device) -> None:
+        """Bring the device scalars up to date with ``group["lr"]`` (schedulers write there); never while
+        a graph is being captured, where the fill would be frozen into the graph."""
+        if torch.cuda.is_current_stream_capturing():
+            if self._lr_dev is None:
+                raise RuntimeError("FusedLARS: run a step before capturing one (the device state is created there)")
+            return
+        if self._lr_dev is None or self._lr_dev.device != device or len(self._lr_seen) != len(self.param_groups):
+            self._lr_dev = torch.zeros(len(self.param_groups), dtype=torch.float32, device=device)
+            self._lr_seen = [None] * len(self.param_groups)
+            self._tables = {}  # plans hold the array
+        for gi, g in enumerate(self.param_groups):
+            if self._lr_seen[gi] != g["lr"]:
+                self._lr_dev[gi].fill_(g["lr"])
+                self._lr_seen[gi] = g["lr"]
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._lr_seen = [None] * len(self._lr_seen)
+
+    # -- step --------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        from . import conv as _conv
+
+        _conv.join_all_devices()  # late weight gradients of a backward that raised before its own join
+        rows = []  # (group index, group, parameter), bf16 gradients after fp32 ones: fewest launches
+        for gi, group in enumerate(self.param_groups):
+            rows += [(gi, group, p) for p in group["params"] if p.grad is not None and p.numel() > 0]
+        if not rows:
+            return loss
+        rows.sort(key=lambda r: r[2].grad.dtype != torch.float32)
+        ps = [p for _, _, p in rows]
+        for p in ps:
+            st = self.state[p]
+            if "momentum_buffer" not in st:
+                st["momentum_buffer"] = torch.zeros_like(p, dtype=torch.float32)
+        masters = [self._master(p) for p in ps]
+        bufs = [self.state[p]["momentum_buffer"] for p in ps]
+        dev = ps[0].device
+        on_gpu = all(p.is_cuda and p.grad.is_cuda for p in ps)
+        native = on_gpu and _ext.available() and all(
+            (m is not None or p.dtype == torch.float32) and p.grad.dtype in (torch.float32, torch.bfloat16)
+            for p, m in zip(ps, masters))
+        if on_gpu and _ext.gpu_required() and not _ext.available():
+            _ext.require()
+        if not native:
+            self._reference_step(rows, masters, bufs, self._adapt(rows))
+            return loss
+        self._sync_lr(dev)
+        # the plan (device table + workspace) depends on which tensors take part, in which order, and on
+        # their groups' hyper-parameters; the native side checks every tensor's size against it
+        key = (tuple(id(p) for p in ps),
+               tuple((g["weight_decay"], g["eta"], g["eps"], g["momentum"], g["exclude_bias_and_norm"])
+                     for g in self.param_groups))
+        plan = self._tables.get(key)
+        if plan is None:
+            adapt = self._adapt(rows)
+            plan = _ext.require().LarsPlan(
+                [p.numel() for p in ps], [gi for gi, _, _ in rows], adapt, [g["weight_decay"] for _, g, _ in rows],
+                [g["eta"] for _, g, _ in rows], [g["eps"] for _, g, _ in rows], [g["momentum"] for _, g, _ in rows],
+                self._lr_dev, ps[0])
+            # a plan holds a device table and a workspace: keep the few most recent sets (a model whose
+            # set of gradient-less parameters varies would otherwise grow the cache without bound)
+            while len(self._tables) >= self._MAX_PLANS:
+                self._tables.pop(next(iter(self._tables)))
+            self._tables[key] = plan
+        else:
+            self._tables[key] = self._tables.pop(key)  # most recently used last
+        if torch.cuda.is_current_stream_capturing() and plan not in self._captured:
+            self._captured.append(plan)  # a captured graph replays into this plan's memory: never freed
+        fp =[m if m is not None else p for p, m in zip(ps, masters)]
+        shadows = [p if m is not None else None for p, m in zip(ps, masters)]
+        _ext.require().lars_step_list(plan, fp, [p.grad for p in ps], bufs, shadows, self.grad_scale,
+                                      self.max_grad_norm)
+        self.last_grad_norm = plan.grad_norm()
+        self.last_launches = plan.last_launches()
+        return loss
+
+    @staticmethod
+    def _adapt(rows):
+        return [not (g["exclude_bias_and_norm"] and p.ndim <= 1) for _, g, p in rows]
+
+    def _reference_step(self, rows, masters, bufs, adapt):
+        """The formula of the class docstring in torch: fp32 arithmetic, no host read."""
+        gs = [p.grad.float() for _, _, p in rows]
+        gnorms = torch.stack([torch.linalg.vector_norm(g) for g in gs])
+        s = self.grad_scale
+        G = torch.linalg.vector_norm(gnorms) * s
+        if self.max_grad_norm > 0:
+            c = torch.clamp(self.max_grad_norm / (G + 1e-6), max=1.0) * s
+        else:
+            c = torch.full_like(G, s)
+        one = torch.ones_like(G)
+        for (gi, group, p), g, gr, master, buf, a in zip(rows, gs, gnorms, masters, bufs, adapt):
+            target = master if master is not None else p
+            pf = target if target.dtype == torch.float32 else target.float()
+            lr, mu, wd = group["lr"], group["momentum"], (group["weight_decay"] if a else 0.0)
+            trust = one
+            if a:
+                wn, gn = torch.linalg.vector_norm(pf), c * gr
+                trust = torch.where((wn > 0) & (gn > 0), group["eta"] * wn / (gn + wd * wn + group["eps"]), one)
+            d = g * c
+            if wd != 0:
+                d = d.add(pf, alpha=wd)
+            buf.mul_(mu).add_(d * (lr * trust))
+            pf.sub_(buf)
+            if pf is not target:
+                target.copy_(pf)
+            if master is not None:
+                p.copy_(master)
+        self.last_grad_norm = G.reshape(1)
+        self.last_launches = 0

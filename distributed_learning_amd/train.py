@@ -36,7 +36,7 @@ from . import data as D
 from .models import get_spec
 from .ops import nn as dnn
 from .ops.loss import cross_entropy
-from .ops.optim import FusedSGD
+from .ops.optim import FusedLARS, FusedSGD, poly_warmup_lr
 from .timing import EventTimers, Timers
 from .utils.log import Level, print_d
 
@@ -119,6 +119,36 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, map_location=No
     return int(state.get("step", 0))
 
 
+def make_optimizer(config, params, master_weights: bool):
+    """``--optimizer sgd`` (default): the reference's momentum SGD; ``lars``: the fused LARS."""
+    if getattr(config, "optimizer", "sgd") == "lars":
+        return FusedLARS(params, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
+                         eta=getattr(config, "lars_eta", 1e-3), max_grad_norm=getattr(config, "max_grad_norm", 0.0),
+                         master_weights=master_weights)
+    return FusedSGD(params, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
+                    master_weights=master_weights)
+
+
+def lr_schedule(config) -> Optional[Callable[[int], float]]:
+    """batch number (from 0) -> learning rate for ``--warmup_steps`` / ``--total_steps``; None (the learning
+    rate is never touched) without them. Batch ``b`` runs at the schedule's value for step ``b + 1``: the first
+    batch of a warmup already updates (at ``lr / warmup_steps``) instead of spending a forward and backward pass
+    on a zero learning rate, and batch ``warmup_steps - 1`` is the first at the full rate."""
+    warmup, total = getattr(config, "warmup_steps", 0), getattr(config, "total_steps", 0)
+    if warmup <= 0 and total <= 0:
+        return None
+    power = getattr(config, "lr_power", 2.0)
+    return lambda batch: poly_warmup_lr(batch + 1, config.lr, warmup, total, power)
+
+
+def set_lr(optimizer, lr: float) -> None:
+    if hasattr(optimizer, "set_lr"):
+        optimizer.set_lr(lr)  # FusedLARS: also the device scalar its kernels read
+    else:
+        for group in optimizer.param_groups:
+            group["lr"] = lr
+
+
 def worker_process(config, distribute_model: Callable, reducer, experiment_name: str,
                    node_id: Optional[int] = None, worker_id: Optional[int] = None) -> dict:
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -133,8 +163,8 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
         dnn.bf16_weights(model)  # bf16 weights, fp32 masters in the optimizer (bench.py's path)
     model = distribute_model(model, reducer, config.grouping_size, device)
     params = list(getattr(model, "module", model).parameters())
-    optimizer = FusedSGD(params, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
-                         master_weights=prec == "bf16")
+    optimizer = make_optimizer(config, params, master_weights=prec == "bf16")
+    schedule = lr_schedule(config)
     start_step = 0
     if getattr(config, "resume", None):
         start_step = load_checkpoint(config.resume, model, optimizer, map_location=device)
@@ -219,6 +249,8 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
 
             timers.start("optimizer_step")
             ev and ev.start("optimizer_step")
+            if schedule is not None:
+                set_lr(optimizer, schedule(batch_count))
             optimizer.step()
             ev and ev.end("optimizer_step")
             timers.end("optimizer_step")
