@@ -161,6 +161,19 @@ void launch_xent_fwd(const void* logits, const int64_t* target, float* ws, float
 void launch_xent_bwd(const void* logits, const int64_t* target, const float* ws, const float* loss_out,
                      const float* gout, void* dlogits, int B, int C, int dtype, hipStream_t stream);
 
+// Label-smoothed variant with top-1 / top-k counts (same file, a second kernel pair; the pair above is untouched).
+// ws: 4*B + 1 floats (row lse, row loss, row valid, rank of the target's logit: logits above it, ties broken by
+// class index; +inf for an ignored row or a NaN target logit; then the mean loss stats[0] / stats[1], NaN without
+// a valid row). stats[4] = {sum of row losses over valid rows,
+// valid rows, rows with rank < 1, rows with rank < k}, summed by one workgroup in a fixed order.
+// Row loss = lse - (1-eps)*x_t - (eps/C)*sum_c x_c. Backward: dlogits = (softmax - (1-eps)*onehot - eps/C) *
+// gout / stats[1], zeros for ignored rows. B == 0 is allowed (stats all zero).
+void launch_xent_metrics_fwd(const void* logits, const int64_t* target, float* ws, float* stats, int B, int C,
+                             float eps, int k, int dtype, hipStream_t stream);
+void launch_xent_smooth_bwd(const void* logits, const int64_t* target, const float* ws, const float* stats,
+                            const float* gout, void* dlogits, int B, int C, float eps, int dtype,
+                            hipStream_t stream);
+
 // ---- fused BatchNorm + residual + ReLU, NHWC (bn_act.hip) ------------------------------------
 // x/res/y/dy/dx/dres: [M, C] row-major (channels_last activations), C % 8 == 0, 16-byte aligned.
 // ws: 7*C floats (mean, invstd, scale, shift | k1, m1, k2); part: bn_partial_floats(M, C) floats.

@@ -102,4 +102,250 @@ void launch_xent_bwd(const void* logits, const int64_t* target, const float* ws,
                        loss_out, gout, (bf16_t*)dlogits, B, C);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Label-smoothed cross-entropy with top-1 / top-k counts (the second forward/backward pair).
+//
+// Forward rows kernel: one wave per row, each logit loaded once. A lane keeps a running max and a
+// sum rescaled to it (online softmax), the plain sum of its logits (the smoothing term) and how many
+// of its logits outrank the target's; the lanes are merged at the end. The target's logit is read
+// first (one wave-uniform load), so the rank needs no second pass.
+// Rows whose base address and pitch are multiples of 16 bytes move 16 bytes per lane per access;
+// any other layout takes the scalar path.
+// Forward batch kernel: one workgroup, fixed order, no float atomics, like xent_mean_kernel.
+// Backward: one wave per row, row constants (target, lse, gout / count) read once per row.
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct Raw16;  // one 16-byte access: 8 bf16 or 4 fp32
+template <> struct Raw16<bf16_t> {
+  static constexpr int kN = 8;
+  ushort8_t v;
+  __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const ushort8_t*>(p); }
+  __device__ __forceinline__ void store(bf16_t* p) const { *reinterpret_cast<ushort8_t*>(p) = v; }
+  __device__ __forceinline__ float get(int j) const { return bf16_to_f32(v[j]); }
+  __device__ __forceinline__ void set(int j, float f) { v[j] = f32_to_bf16(f); }
+};
+template <> struct Raw16<float> {
+  static constexpr int kN = 4;
+  float4_t v;
+  __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const float4_t*>(p); }
+  __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4_t*>(p) = v; }
+  __device__ __forceinline__ float get(int j) const { return v[j]; }
+  __device__ __forceinline__ void set(int j, float f) { v[j] = f; }
+};
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+// Running (max m, sum s of exp(x - m)) of one lane. A lane that has seen nothing, or only -inf, holds
+// m = -inf and s = 0: nothing is rescaled from m = -inf and a -inf logit adds exactly 0, so
+// exp(-inf - (-inf)) is never formed. A NaN logit still reaches s.
+struct OnlineLse {
+  float m = -INFINITY, s = 0.f;
+  __device__ __forceinline__ void rescale(float mn) {
+    if (m != -INFINITY) s *= __expf(m - mn);
+    m = mn;
+  }
+  __device__ __forceinline__ void add(float x) {  // after rescale() to a max that covers x
+    s += x == -INFINITY ? 0.f : __expf(x - m);
+  }
+};
+
+// What one lane knows about its part of the row.
+struct RowAcc {
+  OnlineLse o;
+  float sum = 0.f;  // plain sum of the logits, for the smoothing term
+  int above = 0;    // logits that outrank the target: larger, or equal with a smaller class index
+  __device__ __forceinline__ void count(float x, int c, float xt, int t) { above += (x > xt) || (x == xt && c < t); }
+};
+
+constexpr int kXUnroll = 4;  // 16-byte loads in flight per lane
+
+template <typename T, bool kVec>
+__global__ __launch_bounds__(kXWaves * 64) void xent_metric_rows_kernel(const T* __restrict__ logits,
+                                                                        const int64_t* __restrict__ target,
+                                                                        float* __restrict__ ws, int B, int C,
+                                                                        float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kXWaves + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const T* x = logits + (int64_t)row * C;
+  const int64_t t64 = target[row];
+  const bool valid = t64 >= 0 && t64 < C;
+  const int t = valid ? (int)t64 : 0;
+  const float xt = Cvt<T>::to_f32(x[t]);  // C >= 1: column 0 exists also for an ignored row
+  RowAcc a;
+  if constexpr (kVec) {
+    constexpr int N = Raw16<T>::kN;
+    const int nvec = C / N;  // exact: the pitch is a multiple of 16 bytes
+    for (int v0 = lane; v0 < nvec; v0 += 64 * kXUnroll) {
+      Raw16<T> r[kXUnroll];
+#pragma unroll
+      for (int u = 0; u < kXUnroll; ++u)
+        if (v0 + 64 * u < nvec) r[u].load(x + (int64_t)(v0 + 64 * u) * N);
+#pragma unroll
+      for (int u = 0; u < kXUnroll; ++u) {
+        if (v0 + 64 * u >= nvec) break;
+        float f[N];
+        float vm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          f[j] = r[u].get(j);
+          vm = fmaxf(vm, f[j]);
+        }
+        a.o.rescale(fmaxf(a.o.m, vm));
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          a.o.add(f[j]);
+          a.sum += f[j];
+          a.count(f[j], (v0 + 64 * u) * N + j, xt, t);
+        }
+      }
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) {
+      const float f = Cvt<T>::to_f32(x[c]);
+      a.o.rescale(fmaxf(a.o.m, f));
+      a.o.add(f);
+      a.sum += f;
+      a.count(f, c, xt, t);
+    }
+  }
+  const float m = wave_max(a.o.m);
+  a.o.rescale(m);  // a lane still at -inf keeps its s (0, or NaN from a NaN logit)
+  const float s = wave_sum(a.o.s);
+  const float sum = wave_sum(a.sum);
+  const int above = wave_sum_int(a.above);
+  if (lane == 0) {
+    const float lse = m + __logf(s);
+    // eps == 0 leaves the sum out (as the plain loss does), so a -inf logit does not turn 0 * inf into NaN
+    const float smooth = eps > 0.f ? eps * (sum / (float)C) : 0.f;
+    ws[row] = lse;
+    ws[B + row] = valid ? lse - (1.f - eps) * xt - smooth : 0.f;
+    ws[2 * B + row] = valid ? 1.f : 0.f;
+    // rank of the target; +inf (never below any k) for an ignored row or a NaN target logit
+    ws[3 * B + row] = (valid && xt == xt) ? (float)above : INFINITY;
+  }
+}
+
+// stats = [sum of row losses over valid rows, valid rows, rows with rank < 1, rows with rank < k];
+// ws[4 * B] = stats[0] / stats[1], the mean loss (NaN without a valid row)
+__global__ __launch_bounds__(256) void xent_stats_kernel(float* __restrict__ ws, float* __restrict__ stats, int B,
+                                                         int k) {
+  __shared__ float red[4][4];
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  const float kf = (float)k;
+  for (int i = threadIdx.x; i < B; i += 256) {
+    const float rank = ws[3 * B + i];
+    acc[0] += ws[B + i];
+    acc[1] += ws[2 * B + i];
+    acc[2] += rank < 1.f ? 1.f : 0.f;
+    acc[3] += rank < kf ? 1.f : 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    acc[q] = wave_sum(acc[q]);
+    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      tot[q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
+      stats[q] = tot[q];
+    }
+    ws[4 * B] = tot[1] > 0.f ? tot[0] / tot[1] : NAN;
+  }
+}
+
+template <typename T, bool kVec>
+__global__ __launch_bounds__(kXWaves * 64) void xent_smooth_bwd_kernel(const T* __restrict__ logits,
+                                                                       const int64_t* __restrict__ target,
+                                                                       const float* __restrict__ ws,
+                                                                       const float* __restrict__ stats,
+                                                                       const float* __restrict__ gout,
+                                                                       T* __restrict__ dlogits, int B, int C,
+                                                                       float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kXWaves + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const T* x = logits + (int64_t)row * C;
+  T* d = dlogits + (int64_t)row * C;
+  const int64_t t64 = target[row];
+  const bool valid = t64 >= 0 && t64 < C;
+  const int t = valid ? (int)t64 : -1;
+  const float lse = ws[row];
+  const float g = valid ? gout[0] / stats[1] : 0.f;  // one division per row
+  const float hot = 1.f - eps, uni = eps / (float)C;
+  if constexpr (kVec) {
+    constexpr int N = Raw16<T>::kN;
+    const int nvec = C / N;
+    for (int v0 = lane; v0 < nvec; v0 += 64 * kXUnroll) {
+      Raw16<T> r[kXUnroll];
+      if (valid) {
+#pragma unroll
+        for (int u = 0; u < kXUnroll; ++u)
+          if (v0 + 64 * u < nvec) r[u].load(x + (int64_t)(v0 + 64 * u) * N);
+      }
+#pragma unroll
+      for (int u = 0; u < kXUnroll; ++u) {
+        if (v0 + 64 * u >= nvec) break;
+        const int c0 = (v0 + 64 * u) * N;
+        Raw16<T> o;
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+          o.set(j, valid ? (__expf(r[u].get(j) - lse) - (c0 + j == t ? hot : 0.f) - uni) * g : 0.f);
+        o.store(d + c0);
+      }
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) {
+      float v = 0.f;
+      if (valid) v = (__expf(Cvt<T>::to_f32(x[c]) - lse) - (c == t ? hot : 0.f) - uni) * g;
+      d[c] = Cvt<T>::from_f32(v);
+    }
+  }
+}
+
+static bool xent_rows_vectorisable(const void* p, int C, int dtype) {
+  const size_t pitch = (size_t)C * (dtype == kF32 ? 4 : 2);
+  return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (pitch % 16 == 0);
+}
+
+void launch_xent_metrics_fwd(const void* logits, const int64_t* target, float* ws, float* stats, int B, int C,
+                             float eps, int k, int dtype, hipStream_t stream) {
+  if (B > 0) {
+    dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
+    const bool vec = xent_rows_vectorisable(logits, C, dtype);
+#define DLA_XENT_ROWS(T, V) \
+  hipLaunchKernelGGL((xent_metric_rows_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target, ws, B, C, eps)
+    if (dtype == kF32) {
+      if (vec) DLA_XENT_ROWS(float, true); else DLA_XENT_ROWS(float, false);
+    } else {
+      if (vec) DLA_XENT_ROWS(bf16_t, true); else DLA_XENT_ROWS(bf16_t, false);
+    }
+#undef DLA_XENT_ROWS
+  }
+  hipLaunchKernelGGL(xent_stats_kernel, dim3(1), dim3(256), 0, stream, ws, stats, B, k);
+}
+
+void launch_xent_smooth_bwd(const void* logits, const int64_t* target, const float* ws, const float* stats,
+                            const float* gout, void* dlogits, int B, int C, float eps, int dtype,
+                            hipStream_t stream) {
+  if (B <= 0) return;
+  dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
+  const bool vec = xent_rows_vectorisable(logits, C, dtype) && xent_rows_vectorisable(dlogits, C, dtype);
+#define DLA_XENT_BWD(T, V)                                                                                         \
+  hipLaunchKernelGGL((xent_smooth_bwd_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target, ws, stats, \
+                     gout, (T*)dlogits, B, C, eps)
+  if (dtype == kF32) {
+    if (vec) DLA_XENT_BWD(float, true); else DLA_XENT_BWD(float, false);
+  } else {
+    if (vec) DLA_XENT_BWD(bf16_t, true); else DLA_XENT_BWD(bf16_t, false);
+  }
+#undef DLA_XENT_BWD
+}
+
 }  // namespace dla

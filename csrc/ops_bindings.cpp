@@ -429,6 +429,50 @@ at::Tensor xent_bwd(at::Tensor logits, at::Tensor target, at::Tensor ws, at::Ten
   return d;
 }
 
+// Counts are carried as floats: below 2^24 rows and classes every count and rank is exact.
+constexpr int64_t kXentMaxDim = int64_t(1) << 24;
+
+static void check_xent_args(const at::Tensor& logits, const at::Tensor& target, double eps, const char* op) {
+  check_dev(logits, "logits");
+  check_dev(target, "target");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), op, ": logits must be a contiguous [B, C]");
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.numel() == logits.size(0) && target.is_contiguous(), op,
+              ": bad target");
+  TORCH_CHECK(target.device() == logits.device(), op, ": logits and target are on different devices");
+  TORCH_CHECK(logits.size(1) >= 1, op, ": no classes");
+  TORCH_CHECK(logits.size(0) < kXentMaxDim && logits.size(1) < kXentMaxDim, op, ": B and C must be below 2^24");
+  TORCH_CHECK(eps >= 0.0 && eps < 1.0, op, ": label smoothing must be in [0, 1), got ", eps);
+}
+
+std::vector<at::Tensor> xent_metrics_fwd(at::Tensor logits, at::Tensor target, double eps, int64_t k) {
+  check_xent_args(logits, target, eps, "xent_metrics_fwd");
+  TORCH_CHECK(k >= 1, "xent_metrics_fwd: k must be >= 1, got ", k);
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto ws = at::empty({4 * (int64_t)B + 1}, f32);
+  auto stats = at::empty({4}, f32);
+  launch_xent_metrics_fwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), stats.data_ptr<float>(),
+                          B, C, (float)eps, (int)std::min(k, kXentMaxDim), dtype_code(logits), current_stream(logits));
+  return {stats, ws};
+}
+
+at::Tensor xent_smooth_bwd(at::Tensor logits, at::Tensor target, at::Tensor ws, at::Tensor stats, at::Tensor gout,
+                           double eps) {
+  check_xent_args(logits, target, eps, "xent_smooth_bwd");
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  check_dev(ws, "ws");
+  check_dev(stats, "stats");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 4 * (int64_t)B + 1, "xent_smooth_bwd: bad workspace");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == 4, "xent_smooth_bwd: bad stats");
+  TORCH_CHECK(gout.is_cuda() && gout.numel() == 1, "xent_smooth_bwd: gout must be one value on the GPU");
+  auto d = at::empty_like(logits);
+  auto g = gout.to(at::kFloat).contiguous();
+  launch_xent_smooth_bwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), stats.data_ptr<float>(),
+                         g.data_ptr<float>(), d.data_ptr(), B, C, (float)eps, dtype_code(logits),
+                         current_stream(logits));
+  return d;
+}
+
 void bind_ops(pybind11::module& m) {
   pybind11::class_<SgdTable>(m, "SgdTable")
       .def(pybind11::init<std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>,
@@ -463,6 +507,10 @@ void bind_ops(pybind11::module& m) {
         pybind11::arg("per_step") = 0);
   m.def("xent_fwd", &xent_fwd, "fused log-softmax + NLL forward");
   m.def("xent_bwd", &xent_bwd, "fused log-softmax + NLL backward");
+  m.def("xent_metrics_fwd", &xent_metrics_fwd,
+        "label-smoothed cross-entropy forward: (stats[4] = loss sum, valid rows, top-1 correct, top-k correct; ws, whose "
+        "last element is the mean loss)");
+  m.def("xent_smooth_bwd", &xent_smooth_bwd, "label-smoothed cross-entropy backward");
 }
 
 }  // namespace dla

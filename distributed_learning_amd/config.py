@@ -62,6 +62,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--total_steps", type=int, default=0,
                    help="polynomial learning-rate decay to 0 at this batch (0 = no decay)")
     p.add_argument("--lr_power", type=float, default=2.0, help="power of the polynomial decay")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="label smoothing of the training loss, in [0, 1) (0 = the plain fused cross-entropy)")
+    p.add_argument("--eval_batches", type=int, default=0,
+                   help="batches per evaluation on held-out data (0 = never evaluate)")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate after every this many batches (0 = once, after the last batch); needs --eval_batches")
+    p.add_argument("--topk", type=int, default=5, help="k of the evaluation's top-k accuracy")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--master_port", type=int, default=29501)
     # MI355X options
@@ -104,6 +111,12 @@ def parse_args(argv: Optional[List[str]] = None):
         parser.error("--max_grad_norm needs --optimizer lars (the fused SGD does not clip)")
     if config.warmup_steps < 0 or config.total_steps < 0:
         parser.error("--warmup_steps and --total_steps must be >= 0")
+    if not 0.0 <= config.label_smoothing < 1.0:
+        parser.error("--label_smoothing must be in [0, 1)")
+    if config.eval_batches < 0 or config.eval_every < 0:
+        parser.error("--eval_batches and --eval_every must be >= 0")
+    if config.topk < 1:
+        parser.error("--topk must be >= 1")
     return finalize(config)
 
 

@@ -183,14 +183,73 @@ class ImageFolder(torch.utils.data.Dataset):
         return (x - self.mean) / self.std, label
 
 
-def load_dataset(kind: str, root: str):
+def load_dataset(kind: str, root: str, train: bool = True):
+    """The training split, or with ``train=False`` the held-out one: MNIST ``t10k``, CIFAR-10
+    ``test_batch.bin``, ImageNet ``root/ImageFolderVal``."""
     if kind == "mnist":
-        return load_mnist(root)
+        return load_mnist(root, train)
     if kind == "cifar10":
-        return load_cifar10(root)
+        return load_cifar10(root, train)
     if kind == "imagenet":
-        return ImageFolder(os.path.join(root, "ImageFolder"))
+        if train:
+            return ImageFolder(os.path.join(root, "ImageFolder"))
+        val = os.path.join(root, "ImageFolderVal")
+        if not os.path.isdir(val):
+            raise FileNotFoundError(f"ImageNet validation tree not found: {val}")
+        return ImageFolder(val)
     raise ValueError(f"unknown dataset kind {kind!r}")
+
+
+class EvalPartition:
+    """A rank's share of a held-out set as equally shaped batches, every sample counted exactly once.
+
+    Rank ``r`` of ``W`` takes samples ``r, r+W, ...`` in file order (no shuffle, nothing dropped). Every rank
+    runs ``len(self)`` batches, the number the largest share needs; what a rank lacks is padded with zero
+    images and target -100, which the loss and the accuracy counts ignore. So collectives inside a batch
+    line up across ranks and the all-reduced counts cover the set exactly."""
+
+    IGNORE = -100
+
+    def __init__(self, dataset, rank: int, world: int, batch_size: int, num_workers: int = 0):
+        if not 0 <= rank < world:
+            raise ValueError(f"rank {rank} outside a world of {world}")
+        self.dataset, self.batch_size, self.num_workers = dataset, int(batch_size), num_workers
+        n = len(dataset)
+        self.index = range(rank, n, world)
+        largest = (n + world - 1) // world
+        self.batches = (largest + self.batch_size - 1) // self.batch_size
+
+    def __len__(self) -> int:
+        return self.batches
+
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        # own generator: the loader's per-iterator seed must not be drawn from the global RNG (an evaluation
+        # leaves the training run's random streams where they were)
+        loader = torch.utils.data.DataLoader(Partition(self.dataset, self.index), batch_size=self.batch_size,
+                                             shuffle=False, num_workers=self.num_workers, drop_last=False,
+                                             generator=torch.Generator().manual_seed(0))
+        shape, dtype, done = None, None, 0
+        for x, y in loader:
+            shape, dtype = tuple(x.shape[1:]), x.dtype
+            y = y.to(torch.long)
+            short = self.batch_size - x.shape[0]
+            if short:
+                x = torch.cat([x, x.new_zeros((short,) + shape)])
+                y = torch.cat([y, y.new_full((short,), self.IGNORE)])
+            done += 1
+            yield x, y
+        if done < self.batches:  # a rank whose share ends a whole batch early
+            if shape is None:
+                x0 = torch.as_tensor(self.dataset[0][0])
+                shape, dtype = tuple(x0.shape), x0.dtype
+            for _ in range(self.batches - done):
+                yield (torch.zeros((self.batch_size,) + shape, dtype=dtype),
+                       torch.full((self.batch_size,), self.IGNORE, dtype=torch.long))
+
+
+def get_eval_loader(dataset, rank: int, world: int, batch_size: int = PER_WORKER_BATCH_SIZE,
+                    num_workers: int = 0) -> EvalPartition:
+    return EvalPartition(dataset, rank, world, batch_size, num_workers)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -3,8 +3,17 @@
 Reference: ``F.log_softmax`` in the model (/root/reference/src/network.py:29,41) followed by
 ``F.nll_loss`` (/root/reference/src/main.py:76). ``cross_entropy(logits, target)`` computes the same
 mean loss in one kernel (csrc/kernels/loss.hip) keeping only the per-row logsumexp for backward.
+
+``cross_entropy_with_metrics`` is the label-smoothed loss together with the batch's top-1 / top-k
+counts, from a second kernel pair in the same file that reads every logit once. The counts follow one
+fixed rule, on the GPU and in the fallback alike: the target's rank is the number of logits above it
+plus the number of equal logits with a smaller class index, and a row is top-k correct iff its rank
+is below k. Ignored rows (target outside ``[0, C)``) and rows whose target logit is NaN are never
+correct.
 """
 from __future__ import annotations
+
+from typing import Tuple
 
 import torch
 import torch.nn.functional as F
@@ -28,8 +37,77 @@ class _XEnt(torch.autograd.Function):
         return C.xent_bwd(logits, target, ws, loss, gout.reshape(1)), None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """Mean cross-entropy over rows with ``target >= 0`` (``ignore_index`` < 0)."""
+class _XEntMetrics(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, eps, k):
+        C = _ext.require()
+        logits = logits.contiguous()
+        target = target.contiguous()
+        stats, ws = C.xent_metrics_fwd(logits, target, eps, k)
+        ctx.save_for_backward(logits, target, ws, stats)
+        ctx.eps = eps
+        ctx.mark_non_differentiable(stats)
+        return ws[-1], stats  # stats[0] / stats[1], divided by the batch kernel
+
+    @staticmethod
+    def backward(ctx, gout, _gstats):
+        logits, target, ws, stats = ctx.saved_tensors
+        C = _ext.require()
+        return C.xent_smooth_bwd(logits, target, ws, stats, gout.reshape(1), ctx.eps), None, None, None
+
+
+def _check_smoothing(label_smoothing: float) -> float:
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+    return eps
+
+
+def _metrics_fallback(logits: torch.Tensor, target: torch.Tensor, eps: float, k: int):
+    """The kernels' semantics in plain torch (CPU tensors, unsupported dtypes, no extension)."""
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    B, C = x.shape
+    valid = (target >= 0) & (target < C)
+    t = torch.where(valid, target, torch.zeros_like(target))
+    xt = x.gather(1, t[:, None]).squeeze(1)
+    row = torch.logsumexp(x, dim=1) - (1.0 - eps) * xt
+    if eps > 0:
+        row = row - (eps / C) * x.sum(dim=1)
+    row = torch.where(valid, row, torch.zeros_like(row))
+    xd, xtd = x.detach(), xt.detach()[:, None]
+    cols = torch.arange(C, device=x.device)[None, :]
+    rank = ((xd > xtd) | ((xd == xtd) & (cols < t[:, None]))).sum(dim=1)
+    ok = valid & ~torch.isnan(xtd[:, 0])
+    total = row.sum()
+    stats = torch.stack([total.detach().float(), valid.sum().float(), (ok & (rank < 1)).sum().float(),
+                         (ok & (rank < k)).sum().float()])
+    return total / stats[1].to(total.dtype), stats
+
+
+def cross_entropy_with_metrics(logits: torch.Tensor, target: torch.Tensor, label_smoothing: float = 0.0,
+                               topk: int = 5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(loss, stats)`` of ``[B, C]`` logits: the mean label-smoothed cross-entropy over the valid rows
+    (differentiable; NaN without one) and the detached float32 ``stats = [sum of row losses, valid rows,
+    top-1 correct, top-k correct]`` on the logits' device. ``loss = stats[0] / stats[1]``; the stats are
+    sums, so they add across batches and all-reduce across ranks with SUM."""
+    eps, k = _check_smoothing(label_smoothing), int(topk)
+    if k < 1:
+        raise ValueError(f"topk must be >= 1, got {topk}")
+    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
+        raise ValueError(f"expected [B, C] logits and [B] targets, got {tuple(logits.shape)} and {tuple(target.shape)}")
+    if logits.is_cuda and logits.dtype in (torch.float32, torch.bfloat16):
+        if _ext.available():
+            return _XEntMetrics.apply(logits, target, eps, k)
+        if _ext.gpu_required():
+            _ext.require()
+    return _metrics_fallback(logits, target, eps, k)
+
+
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:
+    """Mean cross-entropy over rows with ``target >= 0`` (``ignore_index`` < 0); with ``label_smoothing`` > 0
+    the smoothed loss of :func:`cross_entropy_with_metrics`."""
+    if _check_smoothing(label_smoothing) > 0.0:
+        return cross_entropy_with_metrics(logits, target, label_smoothing, topk=1)[0]
     if logits.is_cuda and logits.dim() == 2 and logits.dtype in (torch.float32, torch.bfloat16):
         if _ext.available():
             return _XEnt.apply(logits, target)

@@ -14,6 +14,9 @@ Differences by design:
 * a device-accurate ``*_device_times.csv`` (HIP events) is written beside the parity CSV;
 * only one process writes ``{exp}_config.txt`` (the reference raced all workers on it);
 * optional checkpoint save/resume (the reference had none; SURVEY.md §5.4);
+* optional label smoothing (``--label_smoothing``) and evaluation on held-out data (``--eval_batches``,
+  ``--eval_every``, ``--topk``): :func:`evaluate` runs between two batches, outside every timer row, and
+  appends one line per evaluation to ``{exp}_{node}_{worker}_eval.txt``; without the flags nothing of it runs;
 * on GPU the step is the framework's measured headline path (the one ``bench.py`` times): native
   MFMA convolutions / FC heads and fused BN kernels, bf16 weights with fp32 master weights in the
   fused SGD (``--precision bf16``, default), on-device synthetic batches, and every gradient
@@ -24,6 +27,7 @@ Differences by design:
 from __future__ import annotations
 
 import datetime
+import itertools
 import os
 import time
 from typing import Callable, Optional
@@ -35,7 +39,7 @@ import torch.nn as nn
 from . import data as D
 from .models import get_spec
 from .ops import nn as dnn
-from .ops.loss import cross_entropy
+from .ops.loss import cross_entropy, cross_entropy_with_metrics
 from .ops.optim import FusedLARS, FusedSGD, poly_warmup_lr
 from .timing import EventTimers, Timers
 from .utils.log import Level, print_d
@@ -86,6 +90,62 @@ def _data_for(config, spec, device, rank: int, node_id: int, worker_id: int, dty
                                   channels_last=_channels_last(config, device))
     ds = D.load_dataset(spec.dataset, config.dataset_root)
     return D.get_partition_loader(ds, node_id, worker_id, config.node_dev, config.total_dev, config.batch_size)
+
+
+def _eval_data_for(config, spec, device, rank: int, node_id: int, worker_id: int, dtype=torch.float32):
+    """Held-out batches of ``--eval_batches``: a synthetic stream of its own (rewound before every evaluation,
+    so each one sees the same batches), or this rank's share of the dataset's test split."""
+    if config.random_input or not config.dataset_root or not os.path.isdir(config.dataset_root):
+        return D.SyntheticBatches(config.batch_size, spec.input_shape, spec.num_classes, device,
+                                  dtype=dtype, seed=config.seed + 104729, rank=rank,
+                                  channels_last=_channels_last(config, device))
+    ds = D.load_dataset(spec.dataset, config.dataset_root, train=False)
+    return D.get_eval_loader(ds, node_id * config.node_dev + worker_id, config.total_dev, config.batch_size,
+                             num_workers=2 if spec.dataset == "imagenet" else 0)
+
+
+def evaluate(model: nn.Module, batches, device, precision: str = "fp32", max_batches: int = 0, topk: int = 5) -> dict:
+    """Loss and top-1 / top-k accuracy of ``model`` over up to ``max_batches`` (0 = all) of ``batches``.
+
+    The inner module runs in ``eval()`` mode under ``no_grad`` with the training loop's dtype and layout
+    handling; each batch's ``[loss sum, valid rows, top-1, top-k]`` is added on the device, all-reduced once
+    over the process group if there is one, and read once. Nothing of the training run moves: no parameter,
+    BatchNorm running statistic or optimizer state is written, no global random stream is drawn from, and
+    every module is put back in the mode it had (``train()`` in the training loop)."""
+    inner = getattr(model, "module", model)
+    device = torch.device(device)
+    prec = precision if device.type == "cuda" else "fp32"
+    cl = device.type == "cuda" and prec != "fp32"
+    autocast = torch.autocast("cuda", dtype=torch.bfloat16) if prec == "autocast" \
+        else torch.autocast("cpu", enabled=False)
+    if isinstance(batches, D.SyntheticBatches):
+        batches.seek(0)
+    it = iter(batches)
+    if max_batches and max_batches > 0:
+        it = itertools.islice(it, int(max_batches))
+    total = torch.zeros(4, dtype=torch.float32, device=device)
+    modes = [(m, m.training) for m in inner.modules()]
+    inner.eval()
+    try:
+        with torch.no_grad():
+            for x, y in it:
+                x = x.to(device, non_blocking=True)
+                y = y.to(device, non_blocking=True)
+                if prec == "bf16" and x.is_floating_point() and x.dtype != torch.bfloat16:
+                    x = x.to(torch.bfloat16)
+                if x.dim() == 4 and cl:
+                    x = x.contiguous(memory_format=torch.channels_last)
+                with autocast:
+                    total += cross_entropy_with_metrics(inner(x), y, 0.0, topk)[1]
+    finally:
+        for m, mode in modes:
+            m.training = mode
+    if dist.is_initialized():
+        dist.all_reduce(total, op=dist.ReduceOp.SUM)
+    loss_sum, n, top1, topk_n = total.tolist()  # the one host read
+    nan = float("nan")
+    return {"loss": loss_sum / n if n else nan, "top1": top1 / n if n else nan, "topk": topk_n / n if n else nan,
+            "samples": int(n), "k": int(topk)}
 
 
 def save_checkpoint(path: str, model: nn.Module, optimizer, step: int, extra: Optional[dict] = None) -> None:
@@ -185,6 +245,24 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
     autocast = torch.autocast("cuda", dtype=torch.bfloat16) if prec == "autocast" \
         else torch.autocast("cpu", enabled=False)
     model.train()
+    smoothing = float(getattr(config, "label_smoothing", 0.0))
+    eval_batches, eval_every = int(getattr(config, "eval_batches", 0)), int(getattr(config, "eval_every", 0))
+    eval_set = _eval_data_for(config, spec, device, rank, node_id, worker_id,
+                              dtype=torch.bfloat16 if prec == "bf16" else torch.float32) if eval_batches > 0 else None
+    evals = []
+
+    def run_eval(done: int) -> None:
+        """One evaluation after ``done`` training batches: between two ``batch`` timer rows, never inside one."""
+        t0 = time.time()
+        r = evaluate(model, eval_set, device, prec, eval_batches, getattr(config, "topk", 5))
+        r["batch"], r["seconds"] = done, time.time() - t0
+        evals.append(r)
+        with open(f"{stem}_eval.txt", "a") as f:
+            f.write(f"Worker {node_id}:{worker_id} eval at batch {done}: loss {r['loss']} top1 {r['top1']} "
+                    f"top{r['k']} {r['topk']} samples {r['samples']}\n")
+
+    if eval_set is not None:
+        open(f"{stem}_eval.txt", "w").close()  # this run's evaluations only
 
     losses = []
     # a resumed run continues the original sequence: batch numbering, and the data stream position
@@ -231,7 +309,7 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             ev and ev.start("forward")
             with autocast:
                 out = model(x)
-                loss = cross_entropy(out, y)
+                loss = cross_entropy(out, y, smoothing)
             ev and ev.end("forward")
             timers.end("forward")
 
@@ -267,10 +345,14 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             if ev:
                 ev.end_experiment(experiment_name, extra)
             batch_count += 1
+            if eval_set is not None and eval_every > 0 and batch_count % eval_every == 0:
+                run_eval(batch_count)
 
     if device.type == "cuda":
         torch.cuda.synchronize()
-    wall = time.time() - t_start
+    wall = time.time() - t_start - sum(r["seconds"] for r in evals)  # training time: evaluations taken out
+    if eval_set is not None and (not evals or evals[-1]["batch"] != batch_count):
+        run_eval(batch_count)  # --eval_every 0, or a last batch that is no multiple of it
     values = torch.stack(losses).cpu().tolist() if losses else []
     with open(f"{stem}_loss.txt", "w") as f:
         for i, v in enumerate(values):
@@ -290,5 +372,8 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
     model.cleanup()
     if hasattr(reducer, "cleanup"):
         reducer.cleanup()
-    return {"losses": values, "rows": rows, "wall_s": wall, "batches": batch_count - start_step,
-            "start_step": start_step}
+    result = {"losses": values, "rows": rows, "wall_s": wall, "batches": batch_count - start_step,
+              "start_step": start_step}
+    if eval_set is not None:
+        result["evals"] = evals
+    return result
