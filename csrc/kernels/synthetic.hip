@@ -34,7 +34,10 @@ struct Philox {
   }
 };
 
-__device__ __forceinline__ float u32_to_unit(uint32_t x) {  // [0, 1) with 24-bit resolution
+// [0, 1) with 24-bit resolution in fp32. A bf16 fill rounds this value to nearest, so it is in [0, 1]:
+// a draw >= 1 - 2^-9 becomes exactly 1.0 (probability 2^-9 per element). The stream is kept as it is --
+// recorded bf16 inputs depend on it -- and tests/test_gpu_synthetic.py pins both ranges.
+__device__ __forceinline__ float u32_to_unit(uint32_t x) {
   return (x >> 8) * (1.0f / 16777216.0f);
 }
 

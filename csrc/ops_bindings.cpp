@@ -121,42 +121,57 @@ void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
   const SgdParams hp{(float)lr, (float)momentum, (float)dampening, (float)weight_decay, (float)grad_scale,
                      nesterov ? 1 : 0, first_step ? 1 : 0};
   const int chunk = mt_chunk_elems();
-  hipStream_t st = current_stream(params[0]);
-  SgdList list{};
-  int blocks = 0;
+  // every launch is built, and so every tensor checked, before the first one runs: a bad tensor anywhere
+  // in the list raises with nothing updated
+  struct Launch {
+    SgdList list;
+    int blocks;
+  };
+  std::vector<Launch> launches;
+  Launch cur{};
   auto flush = [&]() {
-    if (list.ntensors == 0) return;
-    list.prefix[list.ntensors] = blocks;
-    launch_sgd_list(list, blocks, gdt, use_m, hp, st);
-    list = SgdList{};
-    blocks = 0;
+    if (cur.list.ntensors == 0) return;
+    cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    launches.push_back(cur);
+    cur = Launch{};
   };
   for (size_t i = 0; i < params.size(); ++i) {
     const at::Tensor& p = params[i];
+    const at::Tensor& g = grads[i];
     check_dev(p, "param");
-    check_dev(grads[i], "grad");
-    TORCH_CHECK(p.scalar_type() == at::kFloat, "sgd_step_list: parameters/masters must be fp32");
-    TORCH_CHECK(dtype_code(grads[i]) == gdt && same_layout(grads[i], p),
+    check_dev(g, "grad");
+    TORCH_CHECK(p.scalar_type() == at::kFloat && p.device() == g.device(),
+                "sgd_step_list: parameters/masters must be fp32 on the gradients' device");
+    TORCH_CHECK(g.device() == grads[0].device(), "sgd_step_list: tensor ", i, " is on another device than the list");
+    TORCH_CHECK(dtype_code(g) == gdt && same_layout(g, p),
                 "sgd_step_list: grad ", i, " must match its parameter's layout and the list's grad dtype");
-    if (p.numel() == 0) continue;
     SgdEntry e{};
     e.param = p.data_ptr<float>();
-    e.grad = grads[i].data_ptr();
+    e.grad = g.data_ptr();
     if (use_m) {
-      TORCH_CHECK(moms[i].scalar_type() == at::kFloat && same_layout(moms[i], p), "bad momentum buffer");
-      e.momentum = moms[i].data_ptr<float>();
+      const at::Tensor& m = moms[i];
+      check_dev(m, "momentum");
+      TORCH_CHECK(m.scalar_type() == at::kFloat && m.device() == g.device() && same_layout(m, p),
+                  "sgd_step_list: bad momentum buffer");
+      e.momentum = m.data_ptr<float>();
     }
     if (!shadows.empty()) {
-      TORCH_CHECK(shadows[i].scalar_type() == at::kBFloat16 && same_layout(shadows[i], p), "bad shadow");
-      e.param_bf16 = reinterpret_cast<uint16_t*>(shadows[i].data_ptr());
+      const at::Tensor& s = shadows[i];
+      check_dev(s, "bf16 shadow");
+      TORCH_CHECK(s.scalar_type() == at::kBFloat16 && s.device() == g.device() && same_layout(s, p),
+                  "sgd_step_list: bad shadow");
+      e.param_bf16 = reinterpret_cast<uint16_t*>(s.data_ptr());
     }
     e.numel = p.numel();
-    list.prefix[list.ntensors] = blocks;
-    list.e[list.ntensors++] = e;
-    blocks += (int)((e.numel + chunk - 1) / chunk);
-    if (list.ntensors == kMaxList) flush();
+    if (e.numel == 0) continue;
+    cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    cur.list.e[cur.list.ntensors++] = e;
+    cur.blocks += (int)((e.numel + chunk - 1) / chunk);
+    if (cur.list.ntensors == kMaxList) flush();
   }
   flush();
+  hipStream_t st = current_stream(grads[0]);
+  for (const Launch& L : launches) launch_sgd_list(L.list, L.blocks, gdt, use_m, hp, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -328,28 +343,33 @@ void pack_tensors_on(const std::vector<at::Tensor>& ts, const std::vector<int64_
   TORCH_CHECK(ts.size() == offs.size(), "pack: tensors/offsets size mismatch");
   const int fdt = dtype_code(flat);
   const int chunk = mt_chunk_elems();
-  PackList list{};
-  int blocks = 0, sdt = -1;
+  // as in sgd_step_list: all launches built and checked first, so a bad slot leaves `flat` untouched
+  struct Launch {
+    PackList list;
+    int blocks, sdt;
+  };
+  std::vector<Launch> launches;
+  Launch cur{};
   auto flush = [&]() {
-    if (list.ntensors == 0) return;
-    list.prefix[list.ntensors] = blocks;
-    launch_pack_list(list, blocks, sdt, fdt, flat.data_ptr(), scale, st);
-    list = PackList{};
-    blocks = 0;
+    if (cur.list.ntensors == 0) return;
+    cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    launches.push_back(cur);
+    cur = Launch{};
   };
   for (size_t i = 0; i < ts.size(); ++i) {
     check_dev(ts[i], "pack tensor");
     const int d = dtype_code(ts[i]);
-    if (sdt != -1 && d != sdt) flush();
-    sdt = d;
-    TORCH_CHECK(offs[i] >= 0 && offs[i] + ts[i].numel() <= flat.numel(), "pack: slot out of range");
+    if (cur.list.ntensors > 0 && d != cur.sdt) flush();
+    cur.sdt = d;
+    TORCH_CHECK(offs[i] >= 0 && offs[i] + ts[i].numel() <= flat.numel(), "pack: slot ", i, " out of range");
     if (ts[i].numel() == 0) continue;
-    list.prefix[list.ntensors] = blocks;
-    list.e[list.ntensors++] = PackEntry{ts[i].data_ptr(), ts[i].numel(), offs[i]};
-    blocks += (int)((ts[i].numel() + chunk - 1) / chunk);
-    if (list.ntensors == kMaxList) flush();
+    cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    cur.list.e[cur.list.ntensors++] = PackEntry{ts[i].data_ptr(), ts[i].numel(), offs[i]};
+    cur.blocks += (int)((ts[i].numel() + chunk - 1) / chunk);
+    if (cur.list.ntensors == kMaxList) flush();
   }
   flush();
+  for (const Launch& L : launches) launch_pack_list(L.list, L.blocks, L.sdt, fdt, flat.data_ptr(), scale, st);
 }
 
 void pack_list(std::vector<at::Tensor> ts, std::vector<int64_t> offs, at::Tensor flat, double scale) {

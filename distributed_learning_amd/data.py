@@ -256,7 +256,9 @@ def get_eval_loader(dataset, rank: int, world: int, batch_size: int = PER_WORKER
 # Synthetic batches
 # ------------------------------------------------------------------------------------------------
 class SyntheticBatches:
-    """Uniform [0,1) images + uniform labels, generated on the training device every step.
+    """Uniform images + uniform labels, generated on the training device every step. fp32 images are in
+    [0, 1); bf16 images are the same fp32 stream rounded to nearest, so they are in [0, 1] -- a draw of
+    1 - 2^-9 or more becomes exactly 1.0 (probability 2^-9 per element).
 
     ``per_rank_seed``: by default each rank draws a different stream (seed + rank), which is what
     data parallelism actually sees; set ``identical=True`` to reproduce the reference, where every

@@ -132,16 +132,21 @@ class FusedSGD(_MasterWeightsOptimizer):
         lr, mom, damp, wd, nest, gsc = (group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
                                         group["nesterov"], group["grad_scale"])
         for p, g, b in zip(ps, gs, bufs):
+            # a low-precision parameter (no master) is updated in fp32 and rounded once: an in-place
+            # p.add_(d) may round the fp32 update to p's dtype before it adds (it does on the GPU)
+            pf = p if p.dtype == torch.float32 else p.float()
             d = g * gsc if gsc != 1.0 else g
             if wd != 0:
-                d = d.add(p, alpha=wd)
+                d = d.add(pf, alpha=wd)
             if mom != 0:
                 if first:
                     b.copy_(d)
                 else:
                     b.mul_(mom).add_(d, alpha=1 - damp)
                 d = d.add(b, alpha=mom) if nest else b
-            p.add_(d, alpha=-lr)
+            pf.add_(d, alpha=-lr)
+            if pf is not p:
+                p.copy_(pf)
 
 
 def poly_warmup_lr(step: int, base_lr: float, warmup_steps: int, total_steps: int, power: float = 2.0,
