@@ -152,6 +152,16 @@ void launch_uniform_fill(void* out, int64_t n, int dtype, uint64_t seed, uint64_
 void launch_randint_fill(int64_t* out, int64_t n, int64_t high, uint64_t seed, uint64_t offset,
                          hipStream_t stream, const int64_t* step = nullptr, uint64_t per_step = 0);
 
+// ---- training augmentation from uint8 batches (augment.hip) ---------------------------------
+// src [N][Hs][Ws][3] uint8 -> out dense [N][Ho][Wo][3] (dtype; any element-aligned address): per-sample crop
+// box geom[n] = (y0, x0, step_y, step_x), bilinear resample, flip[n] != 0 mirrors x, out = fmaf(v, scale[c],
+// bias[c]). pad: width of a virtual black border (0: taps clamp to the edge). geom, flip, scale, bias are
+// device pointers, geom 16-byte aligned. N*Ho*Wo*3 and N*Hs*Ws*3 must be below 2^31 (32-bit element indices)
+// and the source at least three pixels (a row's two x taps are one 8-byte load kept inside the tensor).
+void launch_augment(const uint8_t* src, void* out, int dtype, const float* geom, const uint8_t* flip,
+                    const float* scale, const float* bias, int N, int Hs, int Ws, int Ho, int Wo, int pad,
+                    hipStream_t stream);
+
 // ---- fused log-softmax + NLL (loss.hip) -----------------------------------------------------
 // logits [B, C] (dtype), target [B] int64 (< 0 = ignored). ws: 3*B floats (row lse, row loss,
 // row valid). loss_out[0] = mean loss over valid rows, loss_out[1] = valid row count.

@@ -425,6 +425,46 @@ void randint_(at::Tensor t, int64_t high, int64_t seed, int64_t offset, c10::opt
                       step_ptr(step, t), (uint64_t)per_step);
 }
 
+// out: logical [N, 3, Ho, Wo] in channels-last memory (dense [N, Ho, Wo, 3]), possibly a slice of a larger
+// buffer. Everything is checked before the launch; the kernel indexes elements with 32 bits.
+void augment_(at::Tensor src, at::Tensor out, at::Tensor geom, at::Tensor flip, at::Tensor scale, at::Tensor bias,
+              int64_t pad) {
+  TORCH_CHECK(src.is_cuda() && out.is_cuda() && geom.is_cuda() && flip.is_cuda() && scale.is_cuda() && bias.is_cuda(),
+              "augment_: every tensor must be on the GPU");
+  for (const at::Tensor* t : {&out, &geom, &flip, &scale, &bias})
+    TORCH_CHECK(t->device() == src.device(), "augment_: tensors are on different devices");
+  TORCH_CHECK(src.scalar_type() == at::kByte, "augment_: src must be uint8, got ", src.scalar_type());
+  TORCH_CHECK(src.dim() == 4 && src.size(3) == 3, "augment_: src must be [N, Hs, Ws, 3] (3 channels last)");
+  TORCH_CHECK(src.is_contiguous(), "augment_: src must be contiguous");
+  const int out_dtype = dtype_code(out);
+  TORCH_CHECK(out.dim() == 4 && out.size(1) == 3 && out.size(0) == src.size(0),
+              "augment_: out must be [N, 3, Ho, Wo] with src's N");
+  const int64_t N = src.size(0), Hs = src.size(1), Ws = src.size(2), Ho = out.size(2), Wo = out.size(3);
+  TORCH_CHECK(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "augment_: empty image");
+  const int64_t want[4] = {Ho * Wo * 3, 1, Wo * 3, 3};
+  for (int d = 0; d < 4; ++d)
+    TORCH_CHECK(out.size(d) == 1 || out.stride(d) == want[d],
+                "augment_: out must be channels-last memory (dense [N, Ho, Wo, 3]); stride ", out.stride(d), " of dim ",
+                d, ", expected ", want[d]);
+  TORCH_CHECK(geom.scalar_type() == at::kFloat && geom.dim() == 2 && geom.size(0) == N && geom.size(1) == 4 &&
+                  geom.is_contiguous(),
+              "augment_: geom must be a contiguous fp32 [N, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(geom.data_ptr()) % 16 == 0, "augment_: geom must be 16-byte aligned");
+  // a row's two x taps are read by one 8-byte load that is kept inside the tensor
+  TORCH_CHECK(N == 0 || src.numel() >= 9, "augment_: src must hold at least three pixels");
+  TORCH_CHECK(flip.scalar_type() == at::kByte && flip.dim() == 1 && flip.size(0) == N && flip.is_contiguous(),
+              "augment_: flip must be a contiguous uint8 [N]");
+  for (const at::Tensor* t : {&scale, &bias})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 3 && t->is_contiguous(),
+                "augment_: scale and bias must be contiguous fp32 [3]");
+  TORCH_CHECK(pad >= 0 && pad < (1 << 20), "augment_: pad must be >= 0, got ", pad);
+  TORCH_CHECK(src.numel() < (int64_t(1) << 31) && out.numel() < (int64_t(1) << 31),
+              "augment_: src and out must have fewer than 2^31 elements");
+  launch_augment(src.data_ptr<uint8_t>(), out.data_ptr(), out_dtype, geom.data_ptr<float>(), flip.data_ptr<uint8_t>(),
+                 scale.data_ptr<float>(), bias.data_ptr<float>(), (int)N, (int)Hs, (int)Ws, (int)Ho, (int)Wo, (int)pad,
+                 current_stream(out));
+}
+
 std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor target) {
   check_dev(logits, "logits");
   check_dev(target, "target");
@@ -525,6 +565,10 @@ void bind_ops(pybind11::module& m) {
   m.def("randint_", &randint_, "Philox integer fill in [0, high)", pybind11::arg("t"), pybind11::arg("high"),
         pybind11::arg("seed"), pybind11::arg("offset"), pybind11::arg("step") = pybind11::none(),
         pybind11::arg("per_step") = 0);
+  m.def("augment_", &augment_,
+        "uint8 [N,Hs,Ws,3] -> channels-last [N,3,Ho,Wo]: per-sample crop, bilinear resample, flip, normalise, cast",
+        pybind11::arg("src"), pybind11::arg("out"), pybind11::arg("geom"), pybind11::arg("flip"),
+        pybind11::arg("scale"), pybind11::arg("bias"), pybind11::arg("pad") = 0);
   m.def("xent_fwd", &xent_fwd, "fused log-softmax + NLL forward");
   m.def("xent_bwd", &xent_bwd, "fused log-softmax + NLL backward");
   m.def("xent_metrics_fwd", &xent_metrics_fwd,

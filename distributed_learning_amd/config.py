@@ -69,6 +69,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval_every", type=int, default=0,
                    help="evaluate after every this many batches (0 = once, after the last batch); needs --eval_batches")
     p.add_argument("--topk", type=int, default=5, help="k of the evaluation's top-k accuracy")
+    p.add_argument("--augment", default="none", choices=["none", "standard"],
+                   help="none: the loaders' fixed normalised tensors; standard: raw uint8 batches transformed on the "
+                        "device -- random-resized crop 256 -> 224 + flip (ImageNet models), pad-4 random crop + flip "
+                        "(CIFAR models), centre crop for evaluation")
+    p.add_argument("--aug_scale_min", type=float, default=0.08,
+                   help="smallest area fraction of the random-resized crop, in (0, 1]")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--master_port", type=int, default=29501)
     # MI355X options
@@ -117,6 +123,15 @@ def parse_args(argv: Optional[List[str]] = None):
         parser.error("--eval_batches and --eval_every must be >= 0")
     if config.topk < 1:
         parser.error("--topk must be >= 1")
+    if not 0.0 < config.aug_scale_min <= 1.0:
+        parser.error("--aug_scale_min must be in (0, 1]")
+    if config.augment != "none":
+        from .models import MODELS
+
+        spec = MODELS.get(config.model or config.model_type)
+        if spec is not None and spec.dataset == "mnist":
+            parser.error(f"--augment {config.augment} needs a CIFAR-10 or ImageNet model: MNIST has no raw "
+                         f"3-channel form for the device-side transform")
     return finalize(config)
 
 

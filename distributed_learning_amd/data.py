@@ -138,27 +138,42 @@ def load_mnist(root: str, train: bool = True) -> TensorDataset:
     raise FileNotFoundError(f"MNIST idx files not found under {root}")
 
 
-def load_cifar10(root: str, train: bool = True) -> TensorDataset:
-    """CIFAR-10 binary batches (``cifar-10-batches-bin``); never unpickles anything."""
+def load_cifar10(root: str, train: bool = True, raw: bool = False) -> TensorDataset:
+    """CIFAR-10 binary batches (``cifar-10-batches-bin``); never unpickles anything. ``raw``: the images as
+    stored, uint8 ``[N, 32, 32, 3]`` (HWC), for the device-side transform (ops/augment.py) instead of the
+    normalised fp32 ``[N, 3, 32, 32]`` tensor."""
     d = Path(root) / "cifar-10-batches-bin"
     files = [d / f"data_batch_{i}.bin" for i in range(1, 6)] if train else [d / "test_batch.bin"]
     if not all(f.exists() for f in files):
         raise FileNotFoundError(f"CIFAR-10 binary batches not found under {d}")
-    raw = np.concatenate([np.fromfile(f, dtype=np.uint8).reshape(-1, 3073) for f in files])
-    y = torch.from_numpy(raw[:, 0].astype(np.int64))
-    x = torch.from_numpy(raw[:, 1:].reshape(-1, 3, 32, 32).astype(np.float32) / 255.0)
+    records = np.concatenate([np.fromfile(f, dtype=np.uint8).reshape(-1, 3073) for f in files])
+    y = torch.from_numpy(records[:, 0].astype(np.int64))
+    if raw:
+        return TensorDataset(torch.from_numpy(np.ascontiguousarray(
+            records[:, 1:].reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1))), y)
+    x = torch.from_numpy(records[:, 1:].reshape(-1, 3, 32, 32).astype(np.float32) / 255.0)
     mean = torch.tensor([0.4914, 0.4822, 0.4465]).view(1, 3, 1, 1)
     std = torch.tensor([0.2470, 0.2435, 0.2616]).view(1, 3, 1, 1)
     return TensorDataset((x - mean) / std, y)
 
 
 class ImageFolder(torch.utils.data.Dataset):
-    """``root/<class>/<image>`` tree; Resize(256) -> CenterCrop(224) -> normalise (data.py:116-125)."""
+    """``root/<class>/<image>`` tree; Resize(256) -> CenterCrop(224) -> normalise (data.py:116-125).
+
+    ``raw=True`` stops after the resize and hands over a uint8 ``[256, 256, 3]`` (HWC) staging image: the same
+    bilinear resize of the shorter side to 256, then the centre 256x256 crop. Crop, flip, normalisation and
+    layout then happen on the device (ops/augment.py). The centre 224 box of the staging image is pixel for
+    pixel the default's crop, since ``(w - 256) // 2 + 16 == (w - 224) // 2``. The trade-off: a random-resized
+    crop is drawn from this 256x256 staging image, not from the full-resolution original as torchvision's is,
+    so it never sees the parts of a non-square image outside the centre square nor more than 256 pixels of
+    detail per side; in exchange every sample has one fixed size and the batch is a single uint8 copy."""
 
     EXT = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".webp")
+    STAGE = 256
 
-    def __init__(self, root: str):
+    def __init__(self, root: str, raw: bool = False):
         self.root = Path(root)
+        self.raw = bool(raw)
         self.classes = sorted(p.name for p in self.root.iterdir() if p.is_dir())
         self.samples = [(str(f), ci) for ci, c in enumerate(self.classes) for f in sorted((self.root / c).rglob("*"))
                         if f.suffix.lower() in self.EXT]
@@ -177,26 +192,34 @@ class ImageFolder(torch.utils.data.Dataset):
         s = 256 / min(w, h)
         img = img.resize((max(1, round(w * s)), max(1, round(h * s))), Image.BILINEAR)
         w, h = img.size
+        if self.raw:
+            left, top = (w - self.STAGE) // 2, (h - self.STAGE) // 2
+            img = img.crop((left, top, left + self.STAGE, top + self.STAGE))
+            return torch.from_numpy(np.array(img, dtype=np.uint8)), label
         left, top = (w - 224) // 2, (h - 224) // 2
         img = img.crop((left, top, left + 224, top + 224))
         x = torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1)
         return (x - self.mean) / self.std, label
 
 
-def load_dataset(kind: str, root: str, train: bool = True):
+def load_dataset(kind: str, root: str, train: bool = True, raw: bool = False):
     """The training split, or with ``train=False`` the held-out one: MNIST ``t10k``, CIFAR-10
-    ``test_batch.bin``, ImageNet ``root/ImageFolderVal``."""
+    ``test_batch.bin``, ImageNet ``root/ImageFolderVal``. ``raw``: uint8 HWC images for the device-side
+    transform (CIFAR-10 and ImageNet; MNIST has no raw form)."""
     if kind == "mnist":
+        if raw:
+            raise ValueError("MNIST has no raw (uint8 HWC) form: the device-side augmentation serves the "
+                             "3-channel CIFAR-10 and ImageNet models only")
         return load_mnist(root, train)
     if kind == "cifar10":
-        return load_cifar10(root, train)
+        return load_cifar10(root, train, raw)
     if kind == "imagenet":
         if train:
-            return ImageFolder(os.path.join(root, "ImageFolder"))
+            return ImageFolder(os.path.join(root, "ImageFolder"), raw)
         val = os.path.join(root, "ImageFolderVal")
         if not os.path.isdir(val):
             raise FileNotFoundError(f"ImageNet validation tree not found: {val}")
-        return ImageFolder(val)
+        return ImageFolder(val, raw)
     raise ValueError(f"unknown dataset kind {kind!r}")
 
 

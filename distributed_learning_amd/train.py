@@ -17,6 +17,10 @@ Differences by design:
 * optional label smoothing (``--label_smoothing``) and evaluation on held-out data (``--eval_batches``,
   ``--eval_every``, ``--topk``): :func:`evaluate` runs between two batches, outside every timer row, and
   appends one line per evaluation to ``{exp}_{node}_{worker}_eval.txt``; without the flags nothing of it runs;
+* optional training augmentation (``--augment standard``): the loaders hand over raw uint8 HWC images, ``data2dev``
+  is one uint8 copy plus one kernel (ops/augment.py) that crops, resamples, flips, normalises, casts and lays out
+  the batch with parameters drawn from (seed, partition, batch number); evaluation uses the centre crop through
+  the same kernel; without the flag nothing of it runs;
 * on GPU the step is the framework's measured headline path (the one ``bench.py`` times): native
   MFMA convolutions / FC heads and fused BN kernels, bf16 weights with fp32 master weights in the
   fused SGD (``--precision bf16``, default), on-device synthetic batches, and every gradient
@@ -26,6 +30,7 @@ Differences by design:
 """
 from __future__ import annotations
 
+import copy
 import datetime
 import itertools
 import os
@@ -38,6 +43,7 @@ import torch.nn as nn
 
 from . import data as D
 from .models import get_spec
+from .ops import augment as aug
 from .ops import nn as dnn
 from .ops.loss import cross_entropy, cross_entropy_with_metrics
 from .ops.optim import FusedLARS, FusedSGD, poly_warmup_lr
@@ -88,8 +94,53 @@ def _data_for(config, spec, device, rank: int, node_id: int, worker_id: int, dty
         return D.SyntheticBatches(config.batch_size, spec.input_shape, spec.num_classes, device,
                                   dtype=dtype, seed=config.seed, rank=rank,
                                   channels_last=_channels_last(config, device))
-    ds = D.load_dataset(spec.dataset, config.dataset_root)
+    ds = D.load_dataset(spec.dataset, config.dataset_root, raw=_augmenting(config))
     return D.get_partition_loader(ds, node_id, worker_id, config.node_dev, config.total_dev, config.batch_size)
+
+
+def _augmenting(config) -> bool:
+    return getattr(config, "augment", "none") != "none"
+
+
+def _augmenters(config, spec, device, prec: str, stream: int):
+    """``--augment standard``: the (training, evaluation) transforms ``(raw uint8 batch on the device, batch
+    number) -> model input`` in the step's dtype and layout, through ops/augment.py: random-resized crop 256 -> 224
+    plus flip (ImageNet models) or pad-4 random crop plus flip (CIFAR models) for training, the centre crop for
+    evaluation. The training parameters are a function of (seed, partition ``stream``, batch number) alone."""
+    if spec.dataset == "imagenet":
+        kind, src_hw, pad = "rrc", (D.ImageFolder.STAGE, D.ImageFolder.STAGE), 0
+        mean, std = aug.IMAGENET_MEAN, aug.IMAGENET_STD
+    elif spec.dataset == "cifar10":
+        kind, src_hw, pad = "padcrop", tuple(spec.input_shape[1:]), 4
+        mean, std = aug.CIFAR10_MEAN, aug.CIFAR10_STD
+    else:
+        raise ValueError(f"--augment {config.augment} needs a CIFAR-10 or ImageNet model, not {spec.dataset!r}")
+    out_hw = tuple(spec.input_shape[1:])
+    dtype = torch.bfloat16 if prec == "bf16" else torch.float32
+    cl = _channels_last(config, device)
+
+    def make(kind: str, pad: int):
+        p = aug.AugmentParams(kind, src_hw, out_hw, seed=config.seed, stream=stream,
+                              scale_min=getattr(config, "aug_scale_min", 0.08), pad=pad)
+
+        def apply(x, batch: int):
+            x = aug.augment(x, *p.params(batch, x.shape[0]), mean, std, out_hw, dtype, pad)
+            return x if cl else x.contiguous()  # the fp32 reference-precision path runs NCHW
+
+        return apply
+
+    return make(kind, pad), make("center", 0)
+
+
+def _config_text(config) -> str:
+    """``{exp}_config.txt``: the augmentation flags appear only when set, so a run without them writes the file it
+    always did."""
+    if _augmenting(config):
+        return str(config)
+    shown = copy.copy(config)
+    for k in ("augment", "aug_scale_min"):
+        shown.__dict__.pop(k, None)
+    return str(shown)
 
 
 def _eval_data_for(config, spec, device, rank: int, node_id: int, worker_id: int, dtype=torch.float32):
@@ -99,19 +150,21 @@ def _eval_data_for(config, spec, device, rank: int, node_id: int, worker_id: int
         return D.SyntheticBatches(config.batch_size, spec.input_shape, spec.num_classes, device,
                                   dtype=dtype, seed=config.seed + 104729, rank=rank,
                                   channels_last=_channels_last(config, device))
-    ds = D.load_dataset(spec.dataset, config.dataset_root, train=False)
+    ds = D.load_dataset(spec.dataset, config.dataset_root, train=False, raw=_augmenting(config))
     return D.get_eval_loader(ds, node_id * config.node_dev + worker_id, config.total_dev, config.batch_size,
                              num_workers=2 if spec.dataset == "imagenet" else 0)
 
 
-def evaluate(model: nn.Module, batches, device, precision: str = "fp32", max_batches: int = 0, topk: int = 5) -> dict:
+def evaluate(model: nn.Module, batches, device, precision: str = "fp32", max_batches: int = 0, topk: int = 5,
+             transform: Optional[Callable] = None) -> dict:
     """Loss and top-1 / top-k accuracy of ``model`` over up to ``max_batches`` (0 = all) of ``batches``.
 
     The inner module runs in ``eval()`` mode under ``no_grad`` with the training loop's dtype and layout
     handling; each batch's ``[loss sum, valid rows, top-1, top-k]`` is added on the device, all-reduced once
     over the process group if there is one, and read once. Nothing of the training run moves: no parameter,
     BatchNorm running statistic or optimizer state is written, no global random stream is drawn from, and
-    every module is put back in the mode it had (``train()`` in the training loop)."""
+    every module is put back in the mode it had (``train()`` in the training loop). ``transform`` (``--augment``):
+    the batches are raw uint8 images; ``transform(batch on the device, index)`` makes the model input."""
     inner = getattr(model, "module", model)
     device = torch.device(device)
     prec = precision if device.type == "cuda" else "fp32"
@@ -128,9 +181,11 @@ def evaluate(model: nn.Module, batches, device, precision: str = "fp32", max_bat
     inner.eval()
     try:
         with torch.no_grad():
-            for x, y in it:
+            for i, (x, y) in enumerate(it):
                 x = x.to(device, non_blocking=True)
                 y = y.to(device, non_blocking=True)
+                if transform is not None:
+                    x = transform(x, i)  # already in the step's dtype and layout: what follows leaves it alone
                 if prec == "bf16" and x.is_floating_point() and x.dtype != torch.bfloat16:
                     x = x.to(torch.bfloat16)
                 if x.dim() == 4 and cl:
@@ -233,7 +288,7 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
     os.makedirs(config.folder, exist_ok=True)
     if rank == 0:
         with open(f"{config.folder}/{experiment_name}_config.txt", "w") as f:
-            f.write(str(config))
+            f.write(_config_text(config))
     stem = f"{config.folder}/{experiment_name}_{node_id}_{worker_id}"
     sync_mode = int(config.sync_timers or 0)
     timers = Timers(sync=sync_mode == 1)
@@ -250,11 +305,20 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
     eval_set = _eval_data_for(config, spec, device, rank, node_id, worker_id,
                               dtype=torch.bfloat16 if prec == "bf16" else torch.float32) if eval_batches > 0 else None
     evals = []
+    train_aug = eval_aug = None
+    if _augmenting(config):
+        train_aug, eval_aug = _augmenters(config, spec, device, prec, node_id * config.node_dev + worker_id)
+        if isinstance(train_set, D.SyntheticBatches):
+            print_d(f"--augment {config.augment} ignored: synthetic input is generated in the model's form",
+                    Level.WARNING)
+            train_aug = None
+        if isinstance(eval_set, D.SyntheticBatches):
+            eval_aug = None
 
     def run_eval(done: int) -> None:
         """One evaluation after ``done`` training batches: between two ``batch`` timer rows, never inside one."""
         t0 = time.time()
-        r = evaluate(model, eval_set, device, prec, eval_batches, getattr(config, "topk", 5))
+        r = evaluate(model, eval_set, device, prec, eval_batches, getattr(config, "topk", 5), eval_aug)
         r["batch"], r["seconds"] = done, time.time() - t0
         evals.append(r)
         with open(f"{stem}_eval.txt", "a") as f:
@@ -295,10 +359,13 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             timers.start("data2dev")
             x = x.to(device, non_blocking=True)
             y = y.to(device, non_blocking=True)
-            if prec == "bf16" and x.is_floating_point() and x.dtype != torch.bfloat16:
-                x = x.to(torch.bfloat16)
-            if x.dim() == 4 and cl:
-                x = x.contiguous(memory_format=torch.channels_last)
+            if train_aug is not None:
+                x = train_aug(x, batch_count)  # uint8 in, the step's dtype and layout out: no cast, no re-layout
+            else:
+                if prec == "bf16" and x.is_floating_point() and x.dtype != torch.bfloat16:
+                    x = x.to(torch.bfloat16)
+                if x.dim() == 4 and cl:
+                    x = x.contiguous(memory_format=torch.channels_last)
             timers.end("data2dev")
 
             timers.start("zero_grad")
