@@ -261,7 +261,10 @@ __device__ __forceinline__ void bn_stats_finalize_body(int bx, const void* __res
   const float inv_m = 1.f / (float)M;
   const float dm = S * inv_m;
   const float mean = K + dm;
-  const float var = fmaxf(Q * inv_m - dm * dm, 0.f);
+  // clamp the rounding of Q/M - dm^2 at 0; a select, not fmaxf (which returns its non-NaN operand): a NaN
+  // variance (a NaN or Inf in the channel) stays NaN in invstd and running_var instead of reading as var = 0
+  const float v0 = Q * inv_m - dm * dm;
+  const float var = v0 < 0.f ? 0.f : v0;
   const float invstd = rsqrtf(var + eps);
   const float g = gamma ? gamma[c] : 1.f;
   const float b = beta ? beta[c] : 0.f;
