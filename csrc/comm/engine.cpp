@@ -52,6 +52,7 @@
 
 #include "dla_bindings.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_tables.h"
 #include "ipc.h"
 #include "plan.h"
@@ -141,8 +142,8 @@ static bool needs_reduce_kernel(int code) {
 }
 
 static double comm_timeout_s() {
-  const char* e = std::getenv("DLA_COMM_TIMEOUT_S");
-  return e ? std::atof(e) : 600.0;
+  static Knob k_comm_timeout_s = Knob::real("COMM_TIMEOUT_S", 600.0);
+  return k_comm_timeout_s.real_value();
 }
 
 // ---------------------------------------------------------------------------------------------

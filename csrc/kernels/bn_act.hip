@@ -18,6 +18,7 @@
 // the unfused chain. Partials are reduced in a fixed order -> bitwise reproducible.
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 #include <algorithm>
@@ -25,9 +26,6 @@
 namespace dla {
 
 constexpr int kBNThreads = 256;
-// Row blocks of the two reduction passes (stats, backward reduce): 4 workgroups per CU stream at
-// full bandwidth, and <= 1024 partial rows keep the finalize's reduction at ~2 load round trips.
-constexpr int kRedBlocks = 1024;
 // Rows per thread per streaming-loop iteration (loads of a group issued back to back).
 constexpr int kUnroll = 4;
 
@@ -833,22 +831,15 @@ __global__ __launch_bounds__(kBNThreads) void bn_bwd_dual_apply_kernel(const T* 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// Block target of the reduction passes (statistics / backward reduce): kRedBlocks, or
+// Block target (row blocks) of the reduction passes (statistics / backward reduce): 1024 = 4 workgroups per CU
+// stream at full bandwidth, and <= 1024 partial rows keep the finalize's reduction at ~2 load round trips;
 // DLA_BN_RED_BLOCKS / set_bn_red_blocks() for A/B runs and tests. Above 1024 partial rows the
 // statistics and backward-reduce finalizes read them through bn_partials_fold_kernel
 // (bn_fold_rows); GEMM-epilogue backward partials (ext_part) above 1024 rows use the
 // wave-per-channel bn_bwd_finalize_kernel<4> instead.
-static int g_red_blocks = 0;  // 0: not set (environment / default)
-void set_bn_red_blocks(int blocks) { g_red_blocks = blocks > 0 ? blocks : 0; }
-int bn_red_blocks() {
-  if (g_red_blocks > 0) return g_red_blocks;
-  static const int v = [] {
-    const char* e = std::getenv("DLA_BN_RED_BLOCKS");
-    const int b = e ? std::atoi(e) : 0;
-    return b > 0 ? b : kRedBlocks;
-  }();
-  return v;
-}
+static Knob k_bn_red_blocks = Knob::positive("BN_RED_BLOCKS", 1024);
+void set_bn_red_blocks(int blocks) { k_bn_red_blocks.set(blocks); }
+int bn_red_blocks() { return k_bn_red_blocks.value(); }
 
 void bn_geometry(int64_t M, int C, int* tpr, int* nrb, int* nct, int target_blocks) {
   if (target_blocks <= 0) target_blocks = bn_red_blocks();

@@ -18,6 +18,7 @@
 // The forward epilogue can emit the BatchNorm statistics of Y (as the 1x1 GEMMs do).
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 #include <algorithm>
@@ -615,10 +616,8 @@ __global__ __launch_bounds__(NT, blocks_per_cu(BM, BN, NT)) void conv3x3_wgrad_k
 static int conv_pipeline(int K, int deep) {
   const int forced = mfma_pipeline();
   if (forced >= 0) return forced;
-  static const int env = [] {  // DLA_CONV_PIPE: one loop for all 3x3 passes (A/B runs)
-    const char* e = std::getenv("DLA_CONV_PIPE");
-    return e ? std::atoi(e) : -1;
-  }();
+  static Knob k_conv_pipe = Knob::integer("CONV_PIPE", -1);  // one loop for all 3x3 passes (A/B runs)
+  const int env = k_conv_pipe.value();
   return K >= 256 ? (env >= 0 ? env : deep) : 0;
 }
 
@@ -679,13 +678,8 @@ static void launch_fwd(const bf16_t* x, const bf16_t* w, bf16_t* y, const ConvGe
 // per CU (one block per CU, so the last wave of tiles is a small fraction). Stage 2 at bs1280 (profiles/r5/g54):
 // forward 0.359 -> 0.340 ms, data gradient 0.347 -> 0.341, stride-2 forward equal; step 82.54 -> 82.27 ms same
 // box. DLA_TILE512=0: off (A/B)
-static bool tile512_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_TILE512");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
+static Knob k_tile512 = Knob::on_unless_0("TILE512");
+static bool tile512_enabled() { return k_tile512.on(); }
 
 int pick_conv_tile(int64_t P, int N, int tile, int K, bool wide_ok) {
   if (tile == kTileAuto && wide_ok && tile256_enabled() && tile512_enabled() && N == 128 && K >= 1024 &&
@@ -843,15 +837,10 @@ static bool wgrad_wide(int Cin, int Cout) { return tn256_enabled() && Cout % 256
 // 128 x 256 four-wave tiles (64 x 128 wave tiles: half the LDS fragment reads per MFMA of the 64 x 64 ones, one
 // block per CU) for the Cout = 128 weight gradients (stage 2), whose 9 * Cin columns the 256x256 tiles cannot
 // cover without wasting half the rows. DLA_WGRAD_W4=1 / set_wgrad_w4 (A/B; default off)
-static int g_wgrad_w4 = -1;
-void set_wgrad_w4(int mode) { g_wgrad_w4 = mode < 0 ? -1 : (mode ? 1 : 0); }
+static Knob k_wgrad_w4 = Knob::off_unless_1("WGRAD_W4");
+void set_wgrad_w4(int mode) { k_wgrad_w4.set(mode); }
 static bool wgrad_w4(int Cin, int Cout) {
-  static const bool env = [] {
-    const char* e = std::getenv("DLA_WGRAD_W4");
-    return e && e[0] == '1';
-  }();
-  const bool on = g_wgrad_w4 < 0 ? env : g_wgrad_w4 == 1;
-  return on && !wgrad_wide(Cin, Cout) && Cout == 128 && Cin % 64 == 0;
+  return k_wgrad_w4.on() && !wgrad_wide(Cin, Cout) && Cout == 128 && Cin % 64 == 0;
 }
 
 int conv3x3_wgrad_splits(int N, int H, int W, int Cin, int Cout, int stride) {

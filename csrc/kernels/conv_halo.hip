@@ -25,6 +25,7 @@
 
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 namespace dla {
@@ -431,16 +432,10 @@ __global__ __launch_bounds__(kHNT, 2) void conv3x3_halo_rb_kernel(const bf16_t* 
 // ResNet-50 bs512 (profiles/r5l, after trimming the per-fragment address VALU to one base select):
 // dgrad 0.203-0.220 vs 0.228-0.255 ms, forward 0.225-0.234 vs 0.230-0.252 ms; the forward is
 // bitwise equal to the implicit-GEMM kernel (same tap / k order), so the switch changes no numerics.
-static int halo_mode() {
-  static const int v = [] {
-    const char* e = std::getenv("DLA_HALO");
-    return e ? std::atoi(e) : 2;
-  }();
-  return v;
-}
+static Knob k_halo = Knob::integer("HALO", 2);
 
 bool halo_conv_eligible(int Cin, int Cout, int W, int stride, bool fwd) {
-  return halo_mode() >= (fwd ? 2 : 1) && Cin == kHC && Cout == kHC && stride == 1 && W >= 1 &&
+  return k_halo.value() >= (fwd ? 2 : 1) && Cin == kHC && Cout == kHC && stride == 1 && W >= 1 &&
          2 * W + 2 + kHBM <= 256;
 }
 
@@ -462,11 +457,9 @@ void launch_conv3x3_halo(const void* x, const void* w, void* y, int N, int H, in
   // DLA_HALO_V=3: variant 2 for the forward (it carries the statistics epilogue), variant 1 for the data gradient
   // -- the per-direction winners of profiles/r5j (forward 0.228-0.231 vs 0.238-0.246 ms, data gradient 0.209-0.221
   // vs 0.221-0.233 ms at bs512)
-  static const int ver_env = [] {
-    const char* e = std::getenv("DLA_HALO_V");
-    return e ? std::atoi(e) : 3;  // default 3 since profiles/r6/g32 (step 80.17 vs 80.33 ms median, interleaved x3)
-  }();
-  const int ver = ver_env == 3 ? (stats ? 2 : 1) : ver_env;
+  // default 3 since profiles/r6/g32 (step 80.17 vs 80.33 ms median, interleaved x3)
+  static Knob k_halo_v = Knob::integer("HALO_V", 3);
+  const int ver = k_halo_v.value() == 3 ? (stats ? 2 : 1) : k_halo_v.value();
   const int slots = ver == 1 ? cus : 2 * cus;
   const int per_block = (nstrips + slots - 1) / slots;
   const int grid = (nstrips + per_block - 1) / per_block;
@@ -475,23 +468,17 @@ void launch_conv3x3_halo(const void* x, const void* w, void* y, int N, int H, in
   const bf16_t* ap = (const bf16_t*)addend;
   bf16_t* yp = (bf16_t*)y;
   // DLA_HALO_FASTDIV=0: the integer-division form of the per-strip tap masks (A/B)
-  static const int fast = [] {
-    const char* e = std::getenv("DLA_HALO_FASTDIV");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
+  static Knob k_halo_fastdiv = Knob::on_unless_0("HALO_FASTDIV");
+  const int fast = k_halo_fastdiv.value();
   const FastDiv fW = make_fastdiv((uint32_t)W), fH = make_fastdiv((uint32_t)H);
   const int use_fast = (P < (1 << 24) && W < (1 << 16) && H < (1 << 16)) ? fast : 0;  // fdiv's exact range
   // the variant-1 data gradient stores from registers (kDirect; default since profiles/r6/g34: -0.14 ms/step,
   // interleaved x3); DLA_HALO_DIRECT=0 restores the LDS-staged epilogue
-  static const bool direct = [] {
-    const char* e = std::getenv("DLA_HALO_DIRECT");
-    return !(e && e[0] == '0');
-  }();
+  static Knob k_halo_direct = Knob::on_unless_0("HALO_DIRECT");
+  const bool direct = k_halo_direct.on();
   // DLA_HALO_DIRECT_FWD=1: the variant-2 forward stores from registers as well (A/B)
-  static const bool direct_fwd = [] {
-    const char* e = std::getenv("DLA_HALO_DIRECT_FWD");
-    return e && e[0] == '1';
-  }();
+  static Knob k_halo_direct_fwd = Knob::off_unless_1("HALO_DIRECT_FWD");
+  const bool direct_fwd = k_halo_direct_fwd.on();
   if (ver == 1) {
     if (stats && direct_fwd && !addend)
       hipLaunchKernelGGL((conv3x3_halo_kernel<true, true>), dim3(grid), dim3(kHNT), kHLds, stream, xp, wp, yp, H, W,

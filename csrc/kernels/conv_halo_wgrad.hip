@@ -20,6 +20,7 @@
 
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 namespace dla {
@@ -205,17 +206,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo_wgrad_kernel(const HaloWg
       for (int r = 0; r < 4; ++r) out[((16 * i + 4 * g + r) * 9 + t) * kWC + ci] = acc[t][i][r];
 }
 
-static int g_halo_wgrad = -1;  // -1: environment (DLA_HALO_WGRAD, default on), 0 off, 1 on
-void set_halo_wgrad(int mode) { g_halo_wgrad = mode < 0 ? -1 : (mode ? 1 : 0); }
+static Knob k_halo_wgrad = Knob::on_unless_0("HALO_WGRAD");
+void set_halo_wgrad(int mode) { k_halo_wgrad.set(mode); }
 
 bool halo_wgrad_eligible(int Cin, int Cout, int W, int stride) {
-  static const bool env_on = [] {
-    const char* e = std::getenv("DLA_HALO_WGRAD");
-    return !(e && e[0] == '0');
-  }();
-  const bool on = g_halo_wgrad < 0 ? env_on : g_halo_wgrad == 1;
   // ring: the 2 (W + 2) + 2 halo rows plus three 128-row strips in flight must fit 512 rows
-  return on && Cin == kWC && Cout == kWC && stride == 1 && W >= 1 && 2 * (W + 2) + 2 + 3 * kWS <= kWRing;
+  return k_halo_wgrad.on() && Cin == kWC && Cout == kWC && stride == 1 && W >= 1 && 2 * (W + 2) + 2 + 3 * kWS <= kWRing;
 }
 
 static int halo_wgrad_grid(int64_t Q) {

@@ -23,6 +23,7 @@
 
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 namespace dla {
@@ -276,13 +277,8 @@ static void launch_nt(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb
 // profiles/r5a: 3x3 fwd/dgrad at 14x14 and 7x7 -14..-17 %, 1x1 with K >= 1024 -10..-19 %; shorter K or
 // N < 256 is HBM- or LDS-bound and loses up to 2x). At least ~3/4 of the CUs must get a tile.
 // DLA_TILE256=0 restores the 128-row tiles (A/B).
-bool tile256_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_TILE256");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
+static Knob k_tile256 = Knob::on_unless_0("TILE256");
+bool tile256_enabled() { return k_tile256.on(); }
 
 // K >= 256 wins per shape in isolation (profiles/r4/g04) but not in the step (g05: +0.1 ms): 1024 stays
 static int g_tile256_min_k = 1024;  // A/B setter (set_tile256_min_k)
@@ -291,27 +287,16 @@ void set_tile256_min_k(int k) { g_tile256_min_k = k > 0 ? k : 1024; }
 // (profiles/r6/g10: stage-3 conv3 0.270 vs 0.299 ms, stage-4 conv3 0.202 vs 0.229 ms) while the data gradients
 // with the identity addend lose (0.397 vs 0.354). In the step, interleaved x3 on one box (profiles/r6/g11):
 // 82.30 ms (256) vs 82.40 (512) vs 82.53 (1024). set_tile256_min_k_stats / DLA_TILE256_MIN_K_STATS for A/B
-static int g_tile256_min_k_stats = [] {
-  const char* e = std::getenv("DLA_TILE256_MIN_K_STATS");
-  const int v = e ? std::atoi(e) : 0;
-  return v > 0 ? v : 256;
-}();
-void set_tile256_min_k_stats(int k) { g_tile256_min_k_stats = k > 0 ? k : 256; }
+static Knob k_tile256_min_k_stats = Knob::positive("TILE256_MIN_K_STATS", 256);
+void set_tile256_min_k_stats(int k) { k_tile256_min_k_stats.set(k); }
 
-static int g_gemm256_direct = -1;  // -1: DLA_GEMM256_DIRECT (default off), 0 / 1
-void set_gemm256_direct(int mode) { g_gemm256_direct = mode < 0 ? -1 : (mode ? 1 : 0); }
-bool gemm256_direct_enabled() {
-  if (g_gemm256_direct >= 0) return g_gemm256_direct == 1;
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_GEMM256_DIRECT");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
+static Knob k_gemm256_direct = Knob::off_unless_1("GEMM256_DIRECT");
+void set_gemm256_direct(int mode) { k_gemm256_direct.set(mode); }
+bool gemm256_direct_enabled() { return k_gemm256_direct.on(); }
 
 int pick_tile(int64_t M, int N, int tile, int K, bool wide_ok, bool stats) {
   if (tile != kTileAuto) return tile;
-  const int min_k = stats ? std::min(g_tile256_min_k, g_tile256_min_k_stats) : g_tile256_min_k;
+  const int min_k = stats ? std::min(g_tile256_min_k, k_tile256_min_k_stats.value()) : g_tile256_min_k;
   if (wide_ok && tile256_enabled() && K >= min_k && N % 256 == 0 && ((M + 255) / 256) * (N / 256) >= 192)
     return kTile256x256;
   // the 128-row tiles win at every other ResNet shape, including the small-M layers, so the narrow
@@ -394,41 +379,22 @@ static inline int tn_bm(int Mo) { return Mo <= 64 ? 64 : 128; }
 static inline int tn_bn(int No) { return No <= 64 ? 64 : 128; }
 
 // XCD-aware ordering of split-K grids (DLA_SPLITK_XCD=0 restores the split-major 2-D order, A/B)
-bool splitk_xcd_remap() {
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_SPLITK_XCD");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
+static Knob k_splitk_xcd = Knob::on_unless_0("SPLITK_XCD");
+bool splitk_xcd_remap() { return k_splitk_xcd.on(); }
 
 // Workgroups a split-K weight-gradient launch aims for (tiles x splits): 512 = 2 per CU;
-// DLA_SPLITK_BLOCKS overrides it for A/B runs
-static int g_splitk_blocks = 0;  // set_splitk_blocks(): > 0 overrides the environment / default
-void set_splitk_blocks(int blocks) { g_splitk_blocks = blocks > 0 ? blocks : 0; }
-int splitk_target_blocks() {
-  if (g_splitk_blocks > 0) return g_splitk_blocks;
-  static const int v = [] {
-    const char* e = std::getenv("DLA_SPLITK_BLOCKS");
-    const int b = e ? std::atoi(e) : 0;
-    return b > 0 ? b : 512;
-  }();
-  return v;
-}
+// DLA_SPLITK_BLOCKS / set_splitk_blocks override it for A/B runs
+static Knob k_splitk_blocks = Knob::positive("SPLITK_BLOCKS", 512);
+void set_splitk_blocks(int blocks) { k_splitk_blocks.set(blocks); }
+int splitk_target_blocks() { return k_splitk_blocks.value(); }
 
 // 256x256 8-wave tiles (one block per CU) for weight gradients whose output dims are both
 // multiples of 256 (the stage-3/4 1x1 convs: compute-bound, like the fwd/dgrad shapes pick_tile
 // sends to kTile256x256); DLA_TILE256=0 turns them off with the other 256x256 tiles
 // (DLA_TN256=0 turns off only these and the 3x3 ones, for A/B)
-static int g_tn256 = -1;  // set_tn256(): -1 environment (DLA_TN256, default on), 0 off, 1 on
-void set_tn256(int mode) { g_tn256 = mode < 0 ? -1 : (mode ? 1 : 0); }
-bool tn256_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("DLA_TN256");
-    return !(e && e[0] == '0');
-  }();
-  return (g_tn256 < 0 ? on : g_tn256 == 1) && tile256_enabled();
-}
+static Knob k_tn256 = Knob::on_unless_0("TN256");
+void set_tn256(int mode) { k_tn256.set(mode); }
+bool tn256_enabled() { return k_tn256.on() && tile256_enabled(); }
 static bool tn_wide(int Mo, int No) { return tn256_enabled() && Mo % 256 == 0 && No % 256 == 0; }
 
 int gemm_tn_splits(int Mo, int No, int K) {
@@ -485,10 +451,8 @@ void launch_splitk_reduce(const float* partial, int splits, int64_t n, void* out
   const int64_t nv = n / 4;
   // slab groups per block: the fewest that give >= 512 blocks, at most 64 and at most splits / 2
   // (DLA_SPLITK_SG=0: one thread per output, for A/B runs)
-  static const bool sg_on = [] {
-    const char* e = std::getenv("DLA_SPLITK_SG");
-    return !(e && e[0] == '0');
-  }();
+  static Knob k_splitk_sg = Knob::on_unless_0("SPLITK_SG");
+  const bool sg_on = k_splitk_sg.on();
   int sg = 1;
   while (sg_on && sg < 64 && 2 * sg <= splits / 2 && (nv * sg + 255) / 256 < 512) sg *= 2;
   const bf16_t* D = (const bf16_t*)addend;

@@ -21,6 +21,7 @@
 
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 namespace dla {
@@ -181,15 +182,11 @@ void launch_apply(const ApplyArgs& ap, const bf16_t* B, int64_t ldb, bf16_t* C, 
 // Largest K served (the consumer's conv1 input channels): 512 covers stages 1-2 and the stage-2 -> 3 transition,
 // where the 128-row register-staged tile is also the unfused GEMM's; above it the unfused forward runs on the
 // 256x256 LDS-DMA tile. DLA_APPLY_MAX_K / set_gemm_apply_max_k (<= kGemmApplyMaxK) for A/B.
-static int g_apply_max_k = [] {
-  const char* e = std::getenv("DLA_APPLY_MAX_K");
-  const int v = e ? std::atoi(e) : 0;
-  return v > 0 ? std::min(v, kGemmApplyMaxK) : 512;
-}();
-void set_gemm_apply_max_k(int k) { g_apply_max_k = k > 0 ? std::min(k, kGemmApplyMaxK) : 512; }
+static Knob k_apply_max_k = Knob::positive("APPLY_MAX_K", 512, /*cap=*/kGemmApplyMaxK);
+void set_gemm_apply_max_k(int k) { k_apply_max_k.set(k); }
 
 bool gemm_apply_ok(int64_t M, int N, int K) {
-  return M > 0 && K % kBK == 0 && K >= kBK && K <= g_apply_max_k && N % 64 == 0 && N > 0 &&
+  return M > 0 && K % kBK == 0 && K >= kBK && K <= k_apply_max_k.value() && N % 64 == 0 && N > 0 &&
          M * (int64_t)K * 2 < ((int64_t)1 << 31) && M * (int64_t)N * 2 < ((int64_t)1 << 31);
 }
 

@@ -30,6 +30,7 @@
 
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 namespace dla {
@@ -222,15 +223,8 @@ __global__ __launch_bounds__(256, 2) void gemm_direct_persist_kernel(
 }
 
 // 0 = one block per tile (gemm_direct_kernel); n > 0 = the persistent kernel with n blocks per CU
-static int g_persist = -1;  // -1: environment (DLA_GEMM_PERSIST, default 0)
-int gemm_persist_blocks() {
-  if (g_persist >= 0) return g_persist;
-  static const int env = [] {
-    const char* e = std::getenv("DLA_GEMM_PERSIST");
-    return e ? std::max(0, std::atoi(e)) : 0;
-  }();
-  return env;
-}
+static Knob k_gemm_persist = Knob::integer("GEMM_PERSIST", 0, /*floor=*/0);
+int gemm_persist_blocks() { return k_gemm_persist.value(); }
 
 template <bool S, bool BT, bool ADD, int PIPE>
 void launch_direct_p(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, bf16_t* C, int64_t ldc, int M, int N,
@@ -263,17 +257,11 @@ void launch_direct(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, b
 
 }  // namespace
 
-// -1: environment (DLA_GEMM_DIRECT, default OFF: same step time as the staged tile, profiles/r6/g03), 0 off, 1 on
-static int g_direct = -1;
-void set_gemm_direct(int mode) { g_direct = mode < 0 ? -1 : (mode ? 1 : 0); }
-void set_gemm_persist(int blocks_per_cu) { g_persist = blocks_per_cu; }
-bool gemm_direct_enabled() {
-  static const bool env = [] {
-    const char* e = std::getenv("DLA_GEMM_DIRECT");
-    return e && e[0] == '1';
-  }();
-  return g_direct < 0 ? env : g_direct == 1;
-}
+// default OFF: same step time as the staged tile, profiles/r6/g03
+static Knob k_gemm_direct = Knob::off_unless_1("GEMM_DIRECT");
+void set_gemm_direct(int mode) { k_gemm_direct.set(mode); }
+void set_gemm_persist(int blocks_per_cu) { k_gemm_persist.set(blocks_per_cu); }
+bool gemm_direct_enabled() { return k_gemm_direct.on(); }
 
 bool gemm_direct_ok(int N, int64_t ldc, const void* addend, int64_t ldd) {
   return gemm_direct_enabled() && N % 8 == 0 && ldc % 8 == 0 && (!addend || ldd % 8 == 0);

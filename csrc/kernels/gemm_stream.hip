@@ -26,6 +26,7 @@
 
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 namespace dla {
@@ -467,16 +468,10 @@ constexpr size_t stream_lds_bytes() {
          (kAp ? (size_t)2 * KC * kBK * sizeof(float) : 0);
 }
 
-int g_stream_mode = -1;  // -1: environment (DLA_GEMM_STREAM, default on), 0 off, 1 on (every K <= 256)
-
-bool stream_enabled() {
-  if (g_stream_mode >= 0) return g_stream_mode == 1;
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_GEMM_STREAM");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
+// set_gemm_stream(1) (forced on, unlike on by default) also serves every K = 256 shape: stream_plan
+Knob k_gemm_stream = Knob::on_unless_0("GEMM_STREAM");
+bool stream_enabled() { return k_gemm_stream.on(); }
+bool stream_forced() { return k_gemm_stream.overridden() && k_gemm_stream.on(); }
 
 struct StreamPlan {
   int bn = 0, mg = 0, per_xcd = 0, grid = 0;
@@ -493,7 +488,7 @@ StreamPlan stream_plan(int64_t M, int N, int K, int64_t lda, int64_t ldc, bool b
   StreamPlan p;
   if (add && K > 128) return p;  // 2 blocks per CU: the K = 256 weight panel does not fit 80 KB
   if (!stream_enabled() || M <= 0) return p;
-  if (K != 64 && K != 128 && !(K == 256 && (b_kmajor || g_stream_mode == 1))) return p;
+  if (K != 64 && K != 128 && !(K == 256 && (b_kmajor || stream_forced()))) return p;
   if (N % 64 != 0 || lda % 8 != 0 || ldc % 8 != 0) return p;
   if (M * lda * 2 >= (int64_t)kOOB || M * ldc * 2 >= (int64_t)kOOB) return p;
   return stream_geometry(M, N, add, bnb);
@@ -519,15 +514,8 @@ StreamPlan stream_geometry(int64_t M, int N, bool add, bool bnb) {
 // The ResNet stem forward (7x7 / s2 over 3 channels, stem.hip) on this kernel: K = 256 over the space-to-depth
 // image, Cout = 64 (one 64-column panel), BN statistics in registers. DLA_STEM_STREAM / set_stem_stream (default
 // off: the 128x64 implicit-GEMM tile kernel)
-int g_stem_stream = -1;
-bool stem_stream_enabled() {
-  if (g_stem_stream >= 0) return g_stem_stream == 1;
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_STEM_STREAM");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
+Knob k_stem_stream = Knob::off_unless_1("STEM_STREAM");
+bool stem_stream_enabled() { return k_stem_stream.on(); }
 
 template <int BN, int KC>
 void launch_stream_kc(const StreamArgs& a, int grid, bool kmajor, bool stats, bool add, hipStream_t stream) {
@@ -573,8 +561,8 @@ void launch_stream_kc(const StreamArgs& a, int grid, bool kmajor, bool stats, bo
 
 }  // namespace
 
-void set_gemm_stream(int mode) { g_stream_mode = mode < 0 ? -1 : (mode ? 1 : 0); }
-void set_stem_stream(int mode) { g_stem_stream = mode < 0 ? -1 : (mode ? 1 : 0); }
+void set_gemm_stream(int mode) { k_gemm_stream.set(mode); }
+void set_stem_stream(int mode) { k_stem_stream.set(mode); }
 
 int stem_stream_rows(int64_t P, int Cout) {
   if (!stem_stream_enabled() || Cout != 64 || P <= 0 || P >= (1 << 24)) return 0;

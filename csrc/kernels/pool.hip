@@ -12,6 +12,7 @@
 //           resolved by reading the 1-byte positions instead of re-reading x.
 #include "dla_common.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_mfma.h"
 
 #include <algorithm>
@@ -297,10 +298,8 @@ void launch_maxpool_fwd(const void* x, void* y, uint8_t* pos, int N, int H, int 
   if (nb == 0) return;
   const bool fast = work < (1 << 24);
   // 3x3/s1: separable strips of 4 output rows (DLA_POOL3_SEP=0: generic kernel, 7: strips of 7; A/B)
-  static const int sep3 = [] {
-    const char* e = std::getenv("DLA_POOL3_SEP");
-    return e ? std::atoi(e) : 4;
-  }();
+  static Knob k_pool3_sep = Knob::integer("POOL3_SEP", 4);
+  const int sep3 = k_pool3_sep.value();
   if (k == 3 && s == 1 && (sep3 == 4 || sep3 == 7)) {
     const int nstrip = (OH + sep3 - 1) / sep3;
     PoolGeom gs{N, H, W, C, OH, OW, k, s, p, mm::make_fastdiv(C / 8), mm::make_fastdiv(OW), mm::make_fastdiv(nstrip)};

@@ -5,6 +5,7 @@
 
 #include "dla_bindings.h"
 #include "dla_kernels.h"
+#include "dla_knob.h"
 #include "dla_tables.h"
 
 namespace dla {
@@ -47,13 +48,98 @@ static int64_t cl_row_stride(const at::Tensor& t, const char* what) {
   return ld;
 }
 
+// ---- argument checks shared by the ops below: `op` and `arg` name the op and its argument in the message; whatever
+// a kernel receives as a raw pointer is checked for device, dtype, layout and size here ----
 
-// launch_bn_fwd scratch for GEMM-epilogue statistics [rows][C][2]: the folded rows (>= 1 float)
-static int64_t ext_part_floats(const c10::optional<at::Tensor>& st, int C) {
-  return std::max<int64_t>(1, (int64_t)bn_fold_groups((int)st->size(0)) * C * 2);
+// the tensor, or null when the optional argument is absent or undefined
+static const at::Tensor* opt(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined() ? &*t : nullptr; }
+
+// a BN parameter or running statistic: fp32 contiguous GPU vector of C elements
+static float* f32_vec(const at::Tensor& t, int64_t C, const char* op, const char* arg) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == C, op, ": ", arg,
+              " must be a contiguous fp32 GPU vector of C elements");
+  return t.data_ptr<float>();
+}
+static float* f32_vec(const c10::optional<at::Tensor>& t, int64_t C, const char* op, const char* arg) {
+  return opt(t) ? f32_vec(*t, C, op, arg) : nullptr;
 }
 
-static int64_t partial_floats(int64_t M, int C) { return bn_partial_floats(M, C); }
+// the 7C fp32 workspace of a BN (mean, invstd, scale, shift and the backward coefficients)
+static float* check_ws(const at::Tensor& ws, int64_t C, const char* op, const char* arg) {
+  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() == 7 * C, op, ": ",
+              arg, " must be the contiguous fp32 GPU workspace of 7C elements");
+  return ws.data_ptr<float>();
+}
+
+// a 1-bit ReLU mask over `elems` elements
+static uint8_t* check_bitmask(const at::Tensor& mask, int64_t elems, const char* op, const char* arg) {
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() * 8 >= elems,
+              op, ": ", arg, " must be a contiguous uint8 GPU 1-bit mask, one bit per element");
+  return mask.data_ptr<uint8_t>();
+}
+
+// fp32 [rows, C, 2] partials, contiguous; with slice_ld also a channel slice of wider [rows, Ctot, 2] partials, whose
+// row stride in channels is stored there (0 when contiguous). Returns rows.
+static int check_partials(const at::Tensor& st, int64_t C, const char* op, const char* arg, int* slice_ld = nullptr) {
+  TORCH_CHECK(st.is_cuda() && st.scalar_type() == at::kFloat && st.dim() == 3 && st.size(1) == C && st.size(2) == 2, op,
+              ": ", arg, " must be fp32 [rows, C, 2] GPU partials");
+  if (slice_ld) {
+    TORCH_CHECK(st.stride(2) == 1 && st.stride(1) == 2 && st.stride(0) % 2 == 0 && st.stride(0) >= 2 * C, op, ": ", arg,
+                " must be contiguous or a channel slice of wider partials");
+    *slice_ld = st.stride(0) == 2 * C ? 0 : (int)(st.stride(0) / 2);
+  } else {
+    TORCH_CHECK(st.is_contiguous(), op, ": ", arg, " must be contiguous");
+  }
+  return (int)st.size(0);
+}
+
+// the uint8 window positions a pooling forward wrote beside its output `like`
+static const uint8_t* check_pos(const at::Tensor& pos, const at::Tensor& like, const char* op) {
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kByte && pos.sizes() == like.sizes() &&
+                  pos.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": pos must be the forward's channels_last uint8 positions");
+  return pos.data_ptr<uint8_t>();
+}
+
+// the stem forward's space-to-depth folded input
+static void check_stem_fold(const at::Tensor& xs, const char* op) {
+  TORCH_CHECK(xs.is_cuda() && xs.dim() == 4 && xs.size(3) == 16 && xs.scalar_type() == at::kBFloat16 && xs.is_contiguous(),
+              op, ": xs must be the forward's folded [N, OH, OW, 16] input");
+}
+
+static int out_dtype_code(c10::ScalarType dt, const char* op) {
+  TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16, op, ": out_dtype must be fp32 or bf16");
+  return dt == at::kFloat ? kF32 : kBF16;
+}
+
+// a gradient in the layout the row kernels read: channels_last (4-D) or contiguous (2-D)
+static at::Tensor to_rows_layout(const at::Tensor& dy) {
+  return dy.dim() == 4 ? dy.contiguous(at::MemoryFormat::ChannelsLast) : dy.contiguous();
+}
+
+// scratch of a BN pass that reads GEMM-epilogue partials [rows][C][2]: their folded rows (>= 1 float)
+static int64_t fold_floats(int rows, int C) { return std::max<int64_t>(1, (int64_t)bn_fold_groups(rows) * C * 2); }
+
+// The launch_bn_fwd call of every BN forward. Training: the statistics -- from the producing conv's epilogue partials
+// `stats` when given, else a reduction pass over x -- are finalized into ws and the running statistics updated.
+// Evaluation: ws is the caller's. Then the apply pass into y (+ mask), unless y is null.
+static void bn_forward(const char* op, const at::Tensor& x, const void* res, void* y,
+                       const c10::optional<at::Tensor>& weight, const c10::optional<at::Tensor>& bias,
+                       const c10::optional<at::Tensor>& running_mean, const c10::optional<at::Tensor>& running_var,
+                       double momentum, double eps, at::Tensor& ws, bool relu, bool training,
+                       const c10::optional<at::Tensor>& stats, uint8_t* mask = nullptr, int64_t ldy = 0) {
+  const int C = (int)x.size(1);
+  const int64_t M = rows_of(x);
+  const at::Tensor* st = opt(stats);
+  const int rows = st ? check_partials(*st, C, op, "stats") : 0;
+  at::Tensor part = at::empty({st ? fold_floats(rows, C) : training ? bn_partial_floats(M, C) : 1}, ws.options());
+  float* rm = f32_vec(running_mean, C, op, "running_mean");
+  float* rv = f32_vec(running_var, C, op, "running_var");
+  launch_bn_fwd(x.data_ptr(), res, y, M, C, dtype_code(x), f32_vec(weight, C, op, "weight"),
+                f32_vec(bias, C, op, "bias"), (float)eps, (float)momentum, training ? rm : nullptr,
+                training ? rv : nullptr, ws.data_ptr<float>(), part.data_ptr<float>(), relu, training,
+                current_stream(x), st ? st->data_ptr<float>() : nullptr, rows, mask, ldy);
+}
 
 // Returns (y, ws, mask). ws (7C fp32) carries mean/invstd/scale/shift for backward; mask (uint8,
 // one bit per element) is only produced for ReLU after a residual add in training mode.
@@ -65,54 +151,36 @@ std::vector<at::Tensor> bn_act_fwd(at::Tensor x, c10::optional<at::Tensor> resid
   check_act(x, "x");
   const int C = (int)x.size(1);
   const int64_t M = rows_of(x);
-  const at::Tensor* res = nullptr;
-  if (residual.has_value() && residual->defined()) {
-    check_act(*residual, "residual");
-    TORCH_CHECK(residual->sizes() == x.sizes() && residual->scalar_type() == x.scalar_type(), "residual mismatch");
-    res = &residual.value();
+  const at::Tensor* res = opt(residual);
+  if (res) {
+    check_act(*res, "residual");
+    TORCH_CHECK(res->sizes() == x.sizes() && res->scalar_type() == x.scalar_type(), "bn_act_fwd: residual mismatch");
   }
-  auto f32 = x.options().dtype(at::kFloat);
-  at::Tensor ws = at::empty({7 * (int64_t)C}, f32);
-  auto fptr = [](const c10::optional<at::Tensor>& t) -> float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "BN parameters/stats must be fp32 contiguous");
-    return t->data_ptr<float>();
-  };
-  float* g = fptr(weight);
-  float* b = fptr(bias);
-  float* rm = fptr(running_mean);
-  float* rv = fptr(running_var);
+  at::Tensor ws = at::empty({7 * (int64_t)C}, x.options().dtype(at::kFloat));
   if (!training) {
-    TORCH_CHECK(rm && rv, "eval-mode BN needs running statistics");
+    TORCH_CHECK(opt(running_mean) && opt(running_var), "bn_act_fwd: eval-mode BN needs running statistics");
     // scale/shift from running stats (tiny per-channel torch ops, C elements)
     auto invstd = (running_var->to(at::kFloat) + eps).rsqrt();
-    auto gm = weight.has_value() && weight->defined() ? *weight : at::ones_like(invstd);
-    auto bt = bias.has_value() && bias->defined() ? *bias : at::zeros_like(invstd);
+    auto gm = opt(weight) ? *weight : at::ones_like(invstd);
+    auto bt = opt(bias) ? *bias : at::zeros_like(invstd);
     ws.narrow(0, 0, C).copy_(*running_mean);
     ws.narrow(0, C, C).copy_(invstd);
     ws.narrow(0, 2 * C, C).copy_(gm * invstd);
     ws.narrow(0, 3 * C, C).copy_(bt - *running_mean * gm * invstd);
   }
-  const bool ext = stats.has_value() && stats->defined();
-  if (ext) {
-    TORCH_CHECK(stats->scalar_type() == at::kFloat && stats->is_contiguous() && stats->dim() == 3 &&
-                    stats->size(1) == C && stats->size(2) == 2,
-                "stats must be fp32 [row_blocks, C, 2] partials");
-  }
-  at::Tensor part = at::empty({(training && !ext) ? partial_floats(M, C) : ext ? ext_part_floats(stats, C) : 1}, f32);
   // out: write y into channels [out_channel, out_channel + C) of a wider channels_last tensor (the
   // concatenated output of an Inception block) instead of a fresh one
   at::Tensor y;
   int64_t ldy = 0;
-  if (out.has_value() && out->defined()) {
-    TORCH_CHECK(x.dim() == 4 && out->dim() == 4 && out->is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                    out->scalar_type() == x.scalar_type() && out->size(0) == x.size(0) && out->size(2) == x.size(2) &&
-                    out->size(3) == x.size(3) && out->size(1) % 8 == 0 && out_channel % 8 == 0 && out_channel >= 0 &&
-                    out_channel + C <= out->size(1),
+  if (const at::Tensor* o = opt(out)) {
+    TORCH_CHECK(x.dim() == 4 && o->is_cuda() && o->dim() == 4 && o->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    o->scalar_type() == x.scalar_type() && o->size(0) == x.size(0) && o->size(2) == x.size(2) &&
+                    o->size(3) == x.size(3) && o->size(1) % 8 == 0 && out_channel % 8 == 0 && out_channel >= 0 &&
+                    out_channel + C <= o->size(1),
                 "bn_act_fwd: out must be a channels_last [N, Ctot, H, W] tensor (Ctot, out_channel % 8 == 0) of x's "
                 "dtype and spatial size holding channels [out_channel, out_channel + C)");
-    y = out->narrow(1, out_channel, C);
-    ldy = out->size(1);
+    y = o->narrow(1, out_channel, C);
+    ldy = o->size(1);
   } else {
     y = at::empty_like(x);
   }
@@ -122,10 +190,9 @@ std::vector<at::Tensor> bn_act_fwd(at::Tensor x, c10::optional<at::Tensor> resid
   // (gemm_nt_apply) or by bn_apply_deferred
   TORCH_CHECK(!defer || (training && ldy == 0 && x.scalar_type() == at::kBFloat16),
               "bn_act_fwd: defer needs training mode, bf16 and a fresh output");
-  launch_bn_fwd(x.data_ptr(), res ? res->data_ptr() : nullptr, defer ? nullptr : y.data_ptr(), M, C, dtype_code(x), g, b, (float)eps,
-                (float)momentum, training ? rm : nullptr, training ? rv : nullptr, ws.data_ptr<float>(),
-                part.data_ptr<float>(), relu, training, current_stream(x), ext ? stats->data_ptr<float>() : nullptr,
-                ext ? (int)stats->size(0) : 0, mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, ldy);
+  bn_forward("bn_act_fwd", x, res ? res->data_ptr() : nullptr, defer ? nullptr : y.data_ptr(), weight, bias,
+             running_mean, running_var, momentum, eps, ws, relu, training, stats,
+             mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, ldy);
   return {y, ws, mask};
 }
 
@@ -142,32 +209,15 @@ std::vector<at::Tensor> bn_dual_fwd(at::Tensor x, at::Tensor xd, c10::optional<a
                                     c10::optional<at::Tensor> stats_d, bool defer) {
   check_act(x, "x");
   check_act(xd, "xd");
-  TORCH_CHECK(xd.sizes() == x.sizes() && xd.scalar_type() == x.scalar_type(), "bn_dual: x / xd mismatch");
+  TORCH_CHECK(xd.sizes() == x.sizes() && xd.scalar_type() == x.scalar_type(), "bn_dual_fwd: x / xd mismatch");
   const int C = (int)x.size(1);
   const int64_t M = rows_of(x);
   auto f32 = x.options().dtype(at::kFloat);
-  auto fptr = [](const c10::optional<at::Tensor>& t) -> float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "BN parameters/stats must be fp32 contiguous");
-    return t->data_ptr<float>();
-  };
-  auto finalize = [&](const at::Tensor& in, const c10::optional<at::Tensor>& g, const c10::optional<at::Tensor>& b,
-                      const c10::optional<at::Tensor>& rm, const c10::optional<at::Tensor>& rv, double mom, double ep,
-                      const c10::optional<at::Tensor>& st) {
-    at::Tensor ws = at::empty({7 * (int64_t)C}, f32);
-    const bool ext = st.has_value() && st->defined();
-    if (ext)
-      TORCH_CHECK(st->scalar_type() == at::kFloat && st->is_contiguous() && st->dim() == 3 && st->size(1) == C &&
-                      st->size(2) == 2,
-                  "stats must be fp32 [row_blocks, C, 2] partials");
-    at::Tensor part = at::empty({ext ? ext_part_floats(st, C) : partial_floats(M, C)}, f32);
-    launch_bn_fwd(in.data_ptr(), nullptr, nullptr, M, C, dtype_code(in), fptr(g), fptr(b), (float)ep, (float)mom,
-                  fptr(rm), fptr(rv), ws.data_ptr<float>(), part.data_ptr<float>(), relu, true, current_stream(in),
-                  ext ? st->data_ptr<float>() : nullptr, ext ? (int)st->size(0) : 0);
-    return ws;
-  };
-  at::Tensor ws = finalize(x, weight, bias, running_mean, running_var, momentum, eps, stats);
-  at::Tensor wsd = finalize(xd, weight_d, bias_d, running_mean_d, running_var_d, momentum_d, eps_d, stats_d);
+  at::Tensor ws = at::empty({7 * (int64_t)C}, f32), wsd = at::empty({7 * (int64_t)C}, f32);
+  bn_forward("bn_dual_fwd", x, nullptr, nullptr, weight, bias, running_mean, running_var, momentum, eps, ws, relu, true,
+             stats);
+  bn_forward("bn_dual_fwd (shortcut)", xd, nullptr, nullptr, weight_d, bias_d, running_mean_d, running_var_d,
+             momentum_d, eps_d, wsd, relu, true, stats_d);
   at::Tensor y = at::empty_like(x);
   at::Tensor mask;
   if (relu) mask = at::empty({(M * C + 7) / 8}, x.options().dtype(at::kByte));
@@ -187,26 +237,23 @@ void bn_apply_deferred(at::Tensor x, c10::optional<at::Tensor> r_, at::Tensor ws
               "bn_apply_deferred: x, y must be bf16 tensors of one shape");
   const int C = (int)x.size(1);
   const int64_t M = rows_of(x);
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() == 7 * (int64_t)C, "ws: 7C fp32");
-  if (!(r_.has_value() && r_->defined())) {  // relu(BN(x)), no residual (its backward recomputes the ReLU from x)
-    launch_bn_fwd(x.data_ptr(), nullptr, y.data_ptr(), M, C, kBF16, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr,
-                  ws.data_ptr<float>(), nullptr, true, false, current_stream(x), nullptr, 0, nullptr, 0);
+  float* wp = check_ws(ws, C, "bn_apply_deferred", "ws");
+  const at::Tensor* r = opt(r_);
+  if (!r) {  // relu(BN(x)), no residual (its backward recomputes the ReLU from x)
+    launch_bn_fwd(x.data_ptr(), nullptr, y.data_ptr(), M, C, kBF16, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, wp,
+                  nullptr, true, false, current_stream(x), nullptr, 0, nullptr, 0);
     return;
   }
-  at::Tensor r = *r_;
-  check_act(r, "r");
-  TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.sizes() == x.sizes(), "bn_apply_deferred: r like x");
-  TORCH_CHECK(mask_.has_value() && mask_->defined(), "bn_apply_deferred: a residual needs the ReLU mask");
-  at::Tensor mask = *mask_;
-  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.numel() * 8 >= M * C, "mask: one bit per element");
-  const bool dual = wsd.has_value() && wsd->defined();
-  if (dual) {
-    TORCH_CHECK(wsd->scalar_type() == at::kFloat && wsd->is_contiguous() && wsd->numel() == 7 * (int64_t)C, "wsd: 7C fp32");
-    launch_bn_dual_apply(x.data_ptr(), r.data_ptr(), y.data_ptr(), ws.data_ptr<float>(), wsd->data_ptr<float>(), M, C,
-                         kBF16, true, mask.data_ptr<uint8_t>(), current_stream(x));
+  check_act(*r, "r");
+  TORCH_CHECK(r->scalar_type() == at::kBFloat16 && r->sizes() == x.sizes(), "bn_apply_deferred: r like x");
+  TORCH_CHECK(opt(mask_), "bn_apply_deferred: a residual needs the ReLU mask");
+  uint8_t* mp = check_bitmask(*mask_, M * C, "bn_apply_deferred", "mask");
+  if (opt(wsd)) {
+    launch_bn_dual_apply(x.data_ptr(), r->data_ptr(), y.data_ptr(), wp, check_ws(*wsd, C, "bn_apply_deferred", "wsd"), M,
+                         C, kBF16, true, mp, current_stream(x));
   } else {
-    launch_bn_fwd(x.data_ptr(), r.data_ptr(), y.data_ptr(), M, C, kBF16, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr,
-                  ws.data_ptr<float>(), nullptr, true, false, current_stream(x), nullptr, 0, mask.data_ptr<uint8_t>(), 0);
+    launch_bn_fwd(x.data_ptr(), r->data_ptr(), y.data_ptr(), M, C, kBF16, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr,
+                  wp, nullptr, true, false, current_stream(x), nullptr, 0, mp, 0);
   }
 }
 
@@ -214,7 +261,7 @@ void bn_apply_deferred(at::Tensor x, c10::optional<at::Tensor> r_, at::Tensor ws
 std::vector<at::Tensor> bn_dual_bwd(at::Tensor dy, c10::optional<at::Tensor> mask, at::Tensor x, at::Tensor ws,
                                     c10::optional<at::Tensor> weight, at::Tensor xd, at::Tensor wsd,
                                     c10::optional<at::Tensor> weight_d, bool want_dx) {
-  dy = dy.dim() == 4 ? dy.contiguous(at::MemoryFormat::ChannelsLast) : dy.contiguous();
+  dy = to_rows_layout(dy);
   check_act(dy, "dy");
   check_act(x, "x");
   check_act(xd, "xd");
@@ -223,25 +270,18 @@ std::vector<at::Tensor> bn_dual_bwd(at::Tensor dy, c10::optional<at::Tensor> mas
   TORCH_CHECK(dy.sizes() == x.sizes() && xd.sizes() == x.sizes() && dy.scalar_type() == x.scalar_type() &&
                   xd.scalar_type() == x.scalar_type(),
               "bn_dual_bwd: dy / x / xd mismatch");
-  TORCH_CHECK(ws.numel() == 7 * (int64_t)C && wsd.numel() == 7 * (int64_t)C, "bn_dual_bwd: 7C workspaces");
-  const uint8_t* mp = nullptr;
-  if (mask.has_value() && mask->defined()) {
-    TORCH_CHECK(mask->scalar_type() == at::kByte && mask->numel() * 8 >= M * C, "bn_dual_bwd: bit mask size");
-    mp = mask->data_ptr<uint8_t>();
-  }
+  const uint8_t* mp = opt(mask) ? check_bitmask(*mask, M * C, "bn_dual_bwd", "mask") : nullptr;
   auto f32 = x.options().dtype(at::kFloat);
-  at::Tensor part = at::empty({partial_floats(M, C)}, f32), partd = at::empty({partial_floats(M, C)}, f32);
+  at::Tensor part = at::empty({bn_partial_floats(M, C)}, f32), partd = at::empty({bn_partial_floats(M, C)}, f32);
   // want_dx = false: reductions + finalizes only (ws / wsd then hold the apply coefficients)
   at::Tensor dx = want_dx ? at::empty_like(x) : at::Tensor(), dxd = want_dx ? at::empty_like(xd) : at::Tensor();
   at::Tensor dg = at::empty({C}, f32), db = at::empty({C}, f32), dgd = at::empty({C}, f32), dbd = at::empty({C}, f32);
-  auto gp = [](const c10::optional<at::Tensor>& w) -> const float* {
-    return (w.has_value() && w->defined()) ? w->data_ptr<float>() : nullptr;
-  };
   launch_bn_dual_bwd(dy.data_ptr(), mp, x.data_ptr(), xd.data_ptr(), want_dx ? dx.data_ptr() : nullptr,
-                     want_dx ? dxd.data_ptr() : nullptr, M, C,
-                     dtype_code(x), gp(weight), gp(weight_d), ws.data_ptr<float>(), wsd.data_ptr<float>(),
-                     part.data_ptr<float>(), partd.data_ptr<float>(), dg.data_ptr<float>(), db.data_ptr<float>(),
-                     dgd.data_ptr<float>(), dbd.data_ptr<float>(), current_stream(x));
+                     want_dx ? dxd.data_ptr() : nullptr, M, C, dtype_code(x), f32_vec(weight, C, "bn_dual_bwd", "weight"),
+                     f32_vec(weight_d, C, "bn_dual_bwd", "weight_d"), check_ws(ws, C, "bn_dual_bwd", "ws"),
+                     check_ws(wsd, C, "bn_dual_bwd", "wsd"), part.data_ptr<float>(), partd.data_ptr<float>(),
+                     dg.data_ptr<float>(), db.data_ptr<float>(), dgd.data_ptr<float>(), dbd.data_ptr<float>(),
+                     current_stream(x));
   return {dx, dg, db, dxd, dgd, dbd};
 }
 
@@ -262,65 +302,59 @@ std::vector<at::Tensor> bn_act_bwd(at::Tensor dy, c10::optional<at::Tensor> y, c
       (reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0 && !need_dres && mask_mode != 3) {
     ld_dy = dy.stride(3);
   } else {
-    dy = dy.dim() == 4 ? dy.contiguous(at::MemoryFormat::ChannelsLast) : dy.contiguous();
+    dy = to_rows_layout(dy);
     check_act(dy, "dy");
   }
-  TORCH_CHECK(mask_mode >= 0 && mask_mode <= 3, "bad mask_mode");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 7 * (int64_t)C, "ws must be the 7C fp32 workspace");
+  TORCH_CHECK(mask_mode >= 0 && mask_mode <= 3, "bn_act_bwd: bad mask_mode");
   const void* yp = nullptr;
   const uint8_t* mp = nullptr;
   if (mask_mode == 3) {
-    TORCH_CHECK(y.has_value() && y->defined(), "mask_mode 3 needs y");
+    TORCH_CHECK(opt(y), "bn_act_bwd: mask_mode 3 needs y");
     check_act(*y, "y");
-    TORCH_CHECK(y->sizes() == x.sizes() && y->scalar_type() == x.scalar_type(), "y mismatch");
+    TORCH_CHECK(y->sizes() == x.sizes() && y->scalar_type() == x.scalar_type(), "bn_act_bwd: y mismatch");
     yp = y->data_ptr();
   } else if (mask_mode == 2) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->scalar_type() == at::kByte &&
-                    mask->numel() * 8 >= M * C && mask->is_cuda(),
-                "mask_mode 2 needs the forward's 1-bit mask");
-    mp = mask->data_ptr<uint8_t>();
+    TORCH_CHECK(opt(mask), "bn_act_bwd: mask_mode 2 needs the forward's 1-bit mask");
+    mp = check_bitmask(*mask, M * C, "bn_act_bwd", "mask");
   }
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type(), "dy dtype must match x");
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == x.scalar_type(), "bn_act_bwd: dy must be a GPU tensor of x's dtype");
   auto f32 = x.options().dtype(at::kFloat);
-  const bool ext = ext_part.has_value() && ext_part->defined();
-  if (ext)
-    TORCH_CHECK(ext_part->scalar_type() == at::kFloat && ext_part->is_contiguous() && ext_part->dim() == 3 &&
-                    ext_part->size(1) == C && ext_part->size(2) == 2,
-                "ext_part must be fp32 [rows, C, 2] (sum dy', sum dy'(x-mean)) partials");
-  at::Tensor part = at::empty({ext ? 1 : partial_floats(M, C)}, f32);
+  // ext_part: (sum dy', sum dy'(x-mean)) partials from the producing data gradient's epilogue
+  const at::Tensor* ext = opt(ext_part);
+  const int ext_rows = ext ? check_partials(*ext, C, "bn_act_bwd", "ext_part") : 0;
+  at::Tensor part = at::empty({ext ? 1 : bn_partial_floats(M, C)}, f32);
   // want_dx = false: reduction + finalize only (ws then holds the apply coefficients for a fused consumer)
   at::Tensor dx = want_dx ? at::empty_like(x) : at::Tensor();
   at::Tensor dres = need_dres ? at::empty_like(x) : at::Tensor();
   at::Tensor dg = at::empty({C}, f32), db = at::empty({C}, f32);
-  const float* g = (weight.has_value() && weight->defined()) ? weight->data_ptr<float>() : nullptr;
-  launch_bn_bwd(dy.data_ptr(), yp, mp, x.data_ptr(), want_dx ? dx.data_ptr() : nullptr, need_dres ? dres.data_ptr() : nullptr, M, C,
-                dtype_code(x), g, ws.data_ptr<float>(), part.data_ptr<float>(), dg.data_ptr<float>(),
-                db.data_ptr<float>(), (int)mask_mode, current_stream(x), ext ? ext_part->data_ptr<float>() : nullptr,
-                ext ? (int)ext_part->size(0) : 0, ld_dy);
+  launch_bn_bwd(dy.data_ptr(), yp, mp, x.data_ptr(), want_dx ? dx.data_ptr() : nullptr,
+                need_dres ? dres.data_ptr() : nullptr, M, C, dtype_code(x), f32_vec(weight, C, "bn_act_bwd", "weight"),
+                check_ws(ws, C, "bn_act_bwd", "ws"), part.data_ptr<float>(), dg.data_ptr<float>(), db.data_ptr<float>(),
+                (int)mask_mode, current_stream(x), ext ? ext->data_ptr<float>() : nullptr, ext_rows, ld_dy);
   return {dx, dres, dg, db};
 }
 
 // BN-backward epilogue operands (see BnBwdArgs): x_bn is the BN input laid out like the GEMM output.
-static BnBwdArgs make_bn_bwd(const at::Tensor& x_bn, const at::Tensor& ws, const c10::optional<at::Tensor>& mask,
-                             int64_t mode, int64_t M, int64_t N, int64_t rows, at::Tensor& part) {
+static BnBwdArgs make_bn_bwd(const char* op, const at::Tensor& x_bn, const at::Tensor& ws,
+                             const c10::optional<at::Tensor>& mask, int64_t mode, int64_t M, int64_t N, int64_t rows,
+                             at::Tensor& part) {
   int64_t ldx = 0;
   if (x_bn.dim() == 4 && !x_bn.is_contiguous(at::MemoryFormat::ChannelsLast)) ldx = cl_row_stride(x_bn, "bn epilogue x");
   TORCH_CHECK(x_bn.is_cuda() && x_bn.scalar_type() == at::kBFloat16 && x_bn.numel() == M * N &&
                   (x_bn.dim() == 2 ? x_bn.is_contiguous() : (ldx > 0 || x_bn.is_contiguous(at::MemoryFormat::ChannelsLast))) &&
                   x_bn.size(1) == N,
-              "bn epilogue: x must be the bf16 BN input with the GEMM output's shape (channels_last, or a channel "
+              op, ": x_bn must be the bf16 BN input with the GEMM output's shape (channels_last, or a channel "
               "slice of a wider channels_last tensor)");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 7 * N, "bn epilogue: ws must be the 7C workspace");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "bn epilogue: mode 0 (no ReLU), 1 (recompute) or 2 (bit mask)");
+  float* wp = check_ws(ws, N, op, "ws");
+  TORCH_CHECK(mode >= 0 && mode <= 2, op, ": mode 0 (no ReLU), 1 (recompute) or 2 (bit mask)");
   const uint8_t* mp = nullptr;
   if (mode == 2) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->scalar_type() == at::kByte && mask->numel() * 8 >= M * N,
-                "bn epilogue: mode 2 needs the forward's bit mask");
-    mp = mask->data_ptr<uint8_t>();
+    TORCH_CHECK(opt(mask), op, ": mode 2 needs the forward's bit mask");
+    mp = check_bitmask(*mask, M * N, op, "mask");
   }
   part = at::empty({rows, N, 2}, ws.options());
-  TORCH_CHECK(ldx == 0 || mode != 2, "bn epilogue: the bit mask needs a contiguous x");
-  return BnBwdArgs{x_bn.data_ptr(), ws.data_ptr<float>(), mp, (int)mode, part.data_ptr<float>(), ldx};
+  TORCH_CHECK(ldx == 0 || mode != 2, op, ": the bit mask needs a contiguous x_bn");
+  return BnBwdArgs{x_bn.data_ptr(), wp, mp, (int)mode, part.data_ptr<float>(), ldx};
 }
 
 static void check_mat(const at::Tensor& t, const char* what) {
@@ -332,49 +366,14 @@ static void check_mat(const at::Tensor& t, const char* what) {
   check_span(t, what);
 }
 
-// C = A @ B^T (A [M,K], B [N,K]; or C = A @ B with B [K,N] when b_kmajor) in bf16 with fp32 accumulation. Optionally returns per-row-block
-// column statistics partials [ceil(M/128), N, 2] (sum, sum of squares of the bf16 outputs).
-static const uint8_t* addend_mask_ptr(const c10::optional<at::Tensor>& m, int64_t M, int64_t N, bool add) {
-  if (!m.has_value() || !m->defined()) return nullptr;
-  TORCH_CHECK(add, "addend_mask needs an addend");
-  TORCH_CHECK(m->scalar_type() == at::kByte && m->is_cuda() && m->numel() * 8 >= M * N,
-              "addend_mask must be the uint8 1-bit mask of the addend");
-  return m->data_ptr<uint8_t>();
-}
-
-// addend2: the gradient of the block input's stride-2 subsample, [n, C, H/2, W/2] channels_last,
-// added at the even pixels of the [n*H*W, C] output rows (requires even H, W).
-static const void* addend2_ptr(const c10::optional<at::Tensor>& a2, int64_t M, int64_t N, int64_t H, int64_t W) {
-  if (!a2.has_value() || !a2->defined()) return nullptr;
-  TORCH_CHECK(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && M % (H * W) == 0, "addend2: even H, W dividing M");
-  TORCH_CHECK(a2->scalar_type() == at::kBFloat16 && a2->dim() == 4 && a2->size(1) == N && a2->size(2) == H / 2 &&
-                  a2->size(3) == W / 2 && a2->size(0) == M / (H * W) &&
-                  a2->is_contiguous(at::MemoryFormat::ChannelsLast),
-              "addend2 must be the bf16 channels_last [n, C, H/2, W/2] gradient");
-  return a2->data_ptr();
-}
-
 // Grouped training BN+ReLU (launch_bn_group_fwd / _bwd): the BatchNorms of an Inception block's
 // branches, one launch per pass. bn_concat_*: outputs are channel slices of the concatenated NHWC
 // block output (dy read in place from its gradient); bn_group_*: each output its own tensor.
-static void check_bn_param(const at::Tensor& t, int64_t C, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == C, what,
-              " must be a contiguous fp32 GPU vector of C elements");
-}
-
 static int64_t check_branch(const at::Tensor& y, const at::Tensor& ref, const char* what) {
   const int64_t ld = cl_row_stride(y, what);
   TORCH_CHECK(y.size(0) == ref.size(0) && y.size(2) == ref.size(2) && y.size(3) == ref.size(3), what,
               ": every branch must have the same N, H, W");
   return ld;
-}
-
-// [rows, C, 2] fp32 partials, or a channel slice of a wider [rows, Ctot, 2] tensor: row stride in channels
-static int partials_row_stride(const at::Tensor& st, int64_t C, const char* what) {
-  TORCH_CHECK(st.is_cuda() && st.scalar_type() == at::kFloat && st.dim() == 3 && st.size(1) == C && st.size(2) == 2 &&
-                  st.stride(2) == 1 && st.stride(1) == 2 && st.stride(0) % 2 == 0 && st.stride(0) >= 2 * C,
-              what, " must be fp32 [row_blocks, C, 2] partials (or a channel slice of wider ones)");
-  return st.stride(0) == 2 * C ? 0 : (int)(st.stride(0) / 2);
 }
 
 // forward fields shared by both variants; returns the workspaces (keep: scratch kept alive)
@@ -395,23 +394,18 @@ static std::vector<at::Tensor> group_fwd_fields(BnGroups& G, const std::vector<a
     G.ldx[g] = check_branch(ys[g], ys[0], "y");
     const int C = (int)ys[g].size(1);
     const at::Tensor& st = stats[g];
-    G.ldp[g] = partials_row_stride(st, C, "grouped BN stats");
-    check_bn_param(gammas[g], C, "weight");
-    check_bn_param(betas[g], C, "bias");
-    check_bn_param(rms[g], C, "running_mean");
-    check_bn_param(rvs[g], C, "running_var");
+    G.nrb[g] = check_partials(st, C, "grouped BN", "stats", &G.ldp[g]);
     auto f32 = ys[g].options().dtype(at::kFloat);
     at::Tensor ws = at::empty({7 * (int64_t)C}, f32);
-    keep.push_back(at::empty({std::max<int64_t>(1, (int64_t)bn_fold_groups((int)st.size(0)) * C * 2)}, f32));
+    keep.push_back(at::empty({fold_floats(G.nrb[g], C)}, f32));
     G.x[g] = (const uint16_t*)ys[g].data_ptr();
     G.C[g] = C;
-    G.nrb[g] = (int)st.size(0);
     G.part[g] = st.data_ptr<float>();
     G.wpart[g] = keep.back().data_ptr<float>();
-    G.gamma[g] = gammas[g].data_ptr<float>();
-    G.beta[g] = betas[g].data_ptr<float>();
-    G.rm[g] = rms[g].data_ptr<float>();
-    G.rv[g] = rvs[g].data_ptr<float>();
+    G.gamma[g] = f32_vec(gammas[g], C, "grouped BN", "weight");
+    G.beta[g] = f32_vec(betas[g], C, "grouped BN", "bias");
+    G.rm[g] = f32_vec(rms[g], C, "grouped BN", "running_mean");
+    G.rv[g] = f32_vec(rvs[g], C, "grouped BN", "running_var");
     G.ws[g] = ws.data_ptr<float>();
     G.eps[g] = (float)epss[g];
     G.mom[g] = (float)moms[g];
@@ -477,8 +471,6 @@ static std::vector<at::Tensor> group_bwd_fields(BnGroups& G, const std::vector<a
   for (int g = 0; g < n; ++g) {
     G.ldx[g] = check_branch(ys[g], ys[0], "y");
     const int C = (int)ys[g].size(1);
-    check_bn_param(gammas[g], C, "weight");
-    TORCH_CHECK(wss[g].scalar_type() == at::kFloat && wss[g].numel() == 7 * (int64_t)C, "ws must be the 7C workspace");
     auto f32 = ys[g].options().dtype(at::kFloat);
     at::Tensor dx, dg = at::empty({C}, f32), db = at::empty({C}, f32);
     if (!dx_out.empty()) {  // written into a given (possibly strided) slice, e.g. of the fan-in's dY
@@ -490,8 +482,8 @@ static std::vector<at::Tensor> group_bwd_fields(BnGroups& G, const std::vector<a
     }
     G.x[g] = (const uint16_t*)ys[g].data_ptr();
     G.C[g] = C;
-    G.gamma[g] = gammas[g].data_ptr<float>();
-    G.ws[g] = wss[g].data_ptr<float>();
+    G.gamma[g] = f32_vec(gammas[g], C, "grouped BN backward", "weight");
+    G.ws[g] = check_ws(wss[g], C, "grouped BN backward", "ws");
     G.dx[g] = (uint16_t*)dx.data_ptr();
     G.dgamma[g] = dg.data_ptr<float>();
     G.dbeta[g] = db.data_ptr<float>();
@@ -553,13 +545,9 @@ std::vector<at::Tensor> bn_group_bwd(std::vector<at::Tensor> dys, std::vector<at
     G.lddy[g] = 0;
     if (!exts.empty()) {
       const at::Tensor& e = exts[g];
-      TORCH_CHECK(e.is_cuda() && e.scalar_type() == at::kFloat && e.is_contiguous() && e.dim() == 3 &&
-                      e.size(1) == G.C[g] && e.size(2) == 2,
-                  "bn_group_bwd: partials must be fp32 [rows, C, 2]");
+      G.nrb[g] = check_partials(e, G.C[g], "bn_group_bwd", "exts");
       G.part[g] = e.data_ptr<float>();
-      G.nrb[g] = (int)e.size(0);
-      keep.push_back(at::empty({std::max<int64_t>(1, (int64_t)bn_fold_groups((int)e.size(0)) * G.C[g] * 2)},
-                               e.options()));
+      keep.push_back(at::empty({fold_floats(G.nrb[g], G.C[g])}, e.options()));
       G.wpart[g] = keep.back().data_ptr<float>();
     }
   }
@@ -570,67 +558,94 @@ std::vector<at::Tensor> bn_group_bwd(std::vector<at::Tensor> dys, std::vector<at
 }
 
 // DLA_GEMM_SPLITK=0 keeps every gemm_nt on the tile kernel (A/B runs)
-static bool split_k_nt() {
-  static const bool v = [] {
-    const char* e = std::getenv("DLA_GEMM_SPLITK");
-    return !(e && e[0] == '0');
-  }();
-  return v;
+static Knob k_gemm_splitk = Knob::on_unless_0("GEMM_SPLITK");
+
+// Operands of gemm_nt / gemm_nt_bn, checked: C = A @ B^T (A [M, K], B [N, K]; or C = A @ B with B [K, N] when
+// b_kmajor) in bf16 with fp32 accumulation, plus the optional epilogue addends.
+struct NtOperands {
+  int M, N, K;
+  at::Tensor C;
+  const void* add = nullptr;  // addend [M, N] rows (row stride ld_add; 0 broadcasts one row)
+  int64_t ld_add = 0;
+  const uint8_t* add_mask = nullptr;  // 1-bit mask applied to the addend
+  // addend2: the gradient of the block input's stride-2 subsample, [n, N, H/2, W/2] channels_last, added at the
+  // even pixels of the [n*H*W, N] output rows (requires even H, W)
+  const void* add2 = nullptr;
+  // the persistent streaming kernel (gemm_stream.hip) can take these addends: none, or the fused identity-gradient
+  // addend (+ ReLU-bit mask) of a data gradient; never the stride-2 second addend
+  bool stream_ok = false;
+};
+
+static NtOperands nt_operands(const char* op, const at::Tensor& A, const at::Tensor& B, bool b_kmajor,
+                              const c10::optional<at::Tensor>& addend, const c10::optional<at::Tensor>& addend_mask,
+                              const c10::optional<at::Tensor>& addend2, int64_t H, int64_t W) {
+  check_mat(A, "A");
+  check_mat(B, "B");
+  TORCH_CHECK(A.size(1) == B.size(b_kmajor ? 0 : 1), op, ": K mismatch");
+  NtOperands o;
+  o.M = (int)A.size(0), o.N = (int)B.size(b_kmajor ? 1 : 0), o.K = (int)A.size(1);
+  const int64_t M = o.M, N = o.N;
+  if (const at::Tensor* d = opt(addend)) {
+    check_mat(*d, "addend");
+    TORCH_CHECK(d->size(0) == M && d->size(1) == N, op, ": addend must be [M, N]");
+    o.add = d->data_ptr();
+    o.ld_add = d->stride(0);
+  }
+  if (const at::Tensor* m = opt(addend_mask)) {
+    TORCH_CHECK(o.add, op, ": addend_mask needs an addend");
+    o.add_mask = check_bitmask(*m, M * N, op, "addend_mask");
+  }
+  if (const at::Tensor* a2 = opt(addend2)) {
+    TORCH_CHECK(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && M % (H * W) == 0, op, ": addend2 needs even H, W dividing M");
+    TORCH_CHECK(a2->is_cuda() && a2->scalar_type() == at::kBFloat16 && a2->dim() == 4 && a2->size(1) == N &&
+                    a2->size(2) == H / 2 && a2->size(3) == W / 2 && a2->size(0) == M / (H * W) &&
+                    a2->is_contiguous(at::MemoryFormat::ChannelsLast),
+                op, ": addend2 must be the bf16 channels_last [n, C, H/2, W/2] gradient");
+    o.add2 = a2->data_ptr();
+  }
+  o.C = at::empty({M, N}, A.options());
+  check_span(o.C, op);
+  o.stream_ok = !o.add2 && (!o.add || (b_kmajor && o.ld_add > 0 && o.ld_add % 8 == 0 &&
+                                       M * o.ld_add * 2 < (int64_t(1) << 31)));
+  return o;
 }
 
+// Optionally returns per-row-block column statistics partials [rows, N, 2] (sum, sum of squares of the bf16 outputs).
 std::vector<at::Tensor> gemm_nt(at::Tensor A, at::Tensor B, bool stats, c10::optional<at::Tensor> addend,
                                 bool b_kmajor, int64_t tile, c10::optional<at::Tensor> addend_mask,
                                 c10::optional<at::Tensor> addend2, int64_t H, int64_t W) {
   TORCH_CHECK(tile >= 0 && tile <= kTile256x256, "gemm_nt: tile config 0..8");
-  check_mat(A, "A");
-  check_mat(B, "B");
-  TORCH_CHECK(A.size(1) == B.size(b_kmajor ? 0 : 1), "gemm_nt: K mismatch");
-  const int M = (int)A.size(0), N = (int)B.size(b_kmajor ? 1 : 0), K = (int)A.size(1);
-  const bool add = addend.has_value() && addend->defined();
-  if (add) {
-    check_mat(*addend, "addend");
-    TORCH_CHECK(addend->size(0) == M && addend->size(1) == N, "gemm_nt: addend must be [M, N]");
-  }
-  at::Tensor C = at::empty({M, N}, A.options());
-  check_span(C, "gemm_nt output");
+  const NtOperands o = nt_operands("gemm_nt", A, B, b_kmajor, addend, addend_mask, addend2, H, W);
+  const int M = o.M, N = o.N, K = o.K;
+  const at::Tensor& C = o.C;
   at::Tensor S;
-  // memory-bound short-K shapes: the persistent streaming kernel (forward with statistics, data gradient
-  // with the fused identity-gradient addend + ReLU-bit mask; not the stride-2 second addend)
-  const bool add2 = addend2.has_value() && addend2->defined();
-  const bool mask = addend_mask.has_value() && addend_mask->defined();
-  const bool stream_ok = tile == kTileAuto && !add2 && (!mask || add) &&
-                         (!add || (b_kmajor && !stats && addend->stride(0) > 0 && addend->stride(0) % 8 == 0 &&
-                                   (int64_t)M * addend->stride(0) * 2 < (int64_t(1) << 31)));
-  const int srows = stream_ok ? gemm_stream_rows(M, N, K, A.stride(0), C.stride(0), b_kmajor, add) : 0;
+  // memory-bound short-K shapes: the streaming kernel (forward with statistics, or data gradient with the addend)
+  const bool stream_ok = o.stream_ok && tile == kTileAuto && !(o.add && stats);
+  const int srows = stream_ok ? gemm_stream_rows(M, N, K, A.stride(0), C.stride(0), b_kmajor, o.add != nullptr) : 0;
   if (srows > 0) {
     if (stats) S = at::empty({srows, N, 2}, A.options().dtype(at::kFloat));
     TORCH_CHECK(launch_gemm_stream(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), b_kmajor, C.data_ptr(),
                                    C.stride(0), M, N, K, stats ? S.data_ptr<float>() : nullptr, current_stream(A),
-                                   add ? addend->data_ptr() : nullptr, add ? addend->stride(0) : 0,
-                                   addend_mask_ptr(addend_mask, M, N, add)),
+                                   o.add, o.ld_add, o.add_mask),
                 "gemm_nt: streaming kernel refused a shape it planned");
     return {C, S};
   }
-  if (stats) S = at::empty({gemm_nt_stats_rows(M, N, (int)tile, K, !add), N, 2},
-                           A.options().dtype(at::kFloat));
+  if (stats) S = at::empty({gemm_nt_stats_rows(M, N, (int)tile, K, !o.add), N, 2}, A.options().dtype(at::kFloat));
   // split-K only for the fully connected heads' shape class: no epilogue features beyond a bias row
   // (a full addend is a conv dgrad's residual sum, whose bitwise result must not depend on which
   // path — tile or split-K — the same sum takes, tests/test_gpu_bn_epilogue.py)
-  const bool plain = !stats && tile == kTileAuto && !(addend_mask.has_value() && addend_mask->defined()) &&
-                     !(addend2.has_value() && addend2->defined()) && (!add || addend->stride(0) == 0);
-  const int splits = plain && M > 0 && N > 0 && split_k_nt() ? gemm_nt_splitk_splits(M, N, K) : 1;
+  const bool plain = !stats && tile == kTileAuto && !o.add_mask && !o.add2 && (!o.add || o.ld_add == 0);
+  const int splits = plain && M > 0 && N > 0 && k_gemm_splitk.on() ? gemm_nt_splitk_splits(M, N, K) : 1;
   if (splits > 1) {  // few output tiles, long K (fully connected heads): split-K + fp32 slab reduce
     at::Tensor P = at::empty({(int64_t)splits * M * N}, A.options().dtype(at::kFloat));
     launch_gemm_nt_splitk(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), b_kmajor, P.data_ptr<float>(), splits,
-                          C.data_ptr(), M, N, K, add ? addend->data_ptr() : nullptr, add ? addend->stride(0) : 0,
-                          current_stream(A));
+                          C.data_ptr(), M, N, K, o.add, o.ld_add, current_stream(A));
     return {C, S};
   }
   if (M > 0 && N > 0)
     launch_gemm_nt(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0), M, N, K,
-                   stats ? S.data_ptr<float>() : nullptr, current_stream(A), add ? addend->data_ptr() : nullptr,
-                   add ? addend->stride(0) : 0, b_kmajor, (int)tile, nullptr, addend_mask_ptr(addend_mask, M, N, add),
-                   addend2_ptr(addend2, M, N, H, W), (int)H, (int)W);
+                   stats ? S.data_ptr<float>() : nullptr, current_stream(A), o.add, o.ld_add, b_kmajor, (int)tile,
+                   nullptr, o.add_mask, o.add2, (int)H, (int)W);
   return {C, S};
 }
 
@@ -649,13 +664,11 @@ std::vector<at::Tensor> gemm_nt_apply(at::Tensor y, at::Tensor r, at::Tensor ws,
   TORCH_CHECK(y.is_contiguous() && r.is_contiguous() && out.is_contiguous() && B.is_contiguous() &&
                   r.sizes() == y.sizes() && out.sizes() == y.sizes() && B.size(1) == K,
               "gemm_nt_apply: y, r, out contiguous [M, K], B contiguous [N, K]");
+  float* wp = check_ws(ws, K, "gemm_nt_apply", "ws");
+  float* wdp = opt(wsd) ? check_ws(*wsd, K, "gemm_nt_apply", "wsd") : nullptr;
+  uint8_t* mp = check_bitmask(mask, M * K, "gemm_nt_apply", "mask");
   TORCH_CHECK(gemm_apply_ok(M, N, K), "gemm_nt_apply: shape not served (check gemm_apply_ok)");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() == 7 * (int64_t)K, "ws: 7K fp32");
-  const bool dual = wsd.has_value() && wsd->defined();
-  if (dual)
-    TORCH_CHECK(wsd->scalar_type() == at::kFloat && wsd->is_contiguous() && wsd->numel() == 7 * (int64_t)K, "wsd: 7K fp32");
-  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kByte && mask.numel() * 8 >= M * K, "mask: one bit per element");
-  const bool sub = xs.has_value() && xs->defined();
+  const bool sub = opt(xs) != nullptr;
   if (sub) {
     TORCH_CHECK(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && M % (H * W) == 0, "gemm_nt_apply: xs needs even H, W");
     TORCH_CHECK(xs->is_cuda() && xs->scalar_type() == at::kBFloat16 && xs->dim() == 4 &&
@@ -667,8 +680,7 @@ std::vector<at::Tensor> gemm_nt_apply(at::Tensor y, at::Tensor r, at::Tensor ws,
   at::Tensor C = at::empty({M, N}, y.options());
   at::Tensor S;
   if (stats) S = at::empty({gemm_apply_rows(M), N, 2}, y.options().dtype(at::kFloat));
-  launch_gemm_apply(y.data_ptr(), r.data_ptr(), ws.data_ptr<float>(), dual ? wsd->data_ptr<float>() : nullptr,
-                    out.data_ptr(), mask.data_ptr<uint8_t>(), B.data_ptr(), B.stride(0), C.data_ptr(), (int)M, N, K,
+  launch_gemm_apply(y.data_ptr(), r.data_ptr(), wp, wdp, out.data_ptr(), mp, B.data_ptr(), B.stride(0), C.data_ptr(), (int)M, N, K,
                     stats ? S.data_ptr<float>() : nullptr, current_stream(y), sub ? xs->data_ptr() : nullptr, (int)H,
                     (int)W);
   return {C, S};
@@ -687,14 +699,14 @@ std::vector<at::Tensor> gemm_nt_stream_apply(at::Tensor y, at::Tensor ws, at::Te
   const int K = (int)y.size(1), N = (int)B.size(0);
   TORCH_CHECK(y.is_contiguous() && out.is_contiguous() && out.sizes() == y.sizes() && B.size(1) == K,
               "gemm_nt_stream_apply: y, out contiguous [M, K], B [N, K]");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() == 7 * (int64_t)K, "ws: 7K fp32");
+  float* wp = check_ws(ws, K, "gemm_nt_stream_apply", "ws");
   const int rows = gemm_stream_rows(M, N, K, K, N, false, false, false);
   TORCH_CHECK(rows > 0, "gemm_nt_stream_apply: shape not served by the streaming kernel");
   at::Tensor C = at::empty({M, N}, y.options());
   at::Tensor S = at::empty({rows, N, 2}, y.options().dtype(at::kFloat));
   TORCH_CHECK(launch_gemm_stream(y.data_ptr(), K, B.data_ptr(), B.stride(0), false, C.data_ptr(), N, (int)M, N, K,
                                  S.data_ptr<float>(), current_stream(y), nullptr, 0, nullptr, nullptr,
-                                 ws.data_ptr<float>(), out.data_ptr()),
+                                 wp, out.data_ptr()),
               "gemm_nt_stream_apply: the streaming kernel refused a shape it planned");
   return {C, S};
 }
@@ -708,38 +720,24 @@ std::vector<at::Tensor> gemm_nt_bn(at::Tensor A, at::Tensor B, c10::optional<at:
                                    at::Tensor x_bn, at::Tensor ws, c10::optional<at::Tensor> mask, int64_t mode,
                                    c10::optional<at::Tensor> addend_mask, c10::optional<at::Tensor> addend2, int64_t H,
                                    int64_t W) {
-  check_mat(A, "A");
-  check_mat(B, "B");
-  TORCH_CHECK(A.size(1) == B.size(b_kmajor ? 0 : 1), "gemm_nt_bn: K mismatch");
-  const int M = (int)A.size(0), N = (int)B.size(b_kmajor ? 1 : 0), K = (int)A.size(1);
-  const bool add = addend.has_value() && addend->defined();
-  if (add) {
-    check_mat(*addend, "addend");
-    TORCH_CHECK(addend->size(0) == M && addend->size(1) == N, "gemm_nt_bn: addend must be [M, N]");
-  }
-  at::Tensor C = at::empty({M, N}, A.options());
-  check_span(C, "gemm_nt_bn output");
+  const NtOperands o = nt_operands("gemm_nt_bn", A, B, b_kmajor, addend, addend_mask, addend2, H, W);
+  const int M = o.M, N = o.N, K = o.K;
+  const at::Tensor& C = o.C;
   at::Tensor part;
   // short-K data gradients: the persistent streaming kernel, whose epilogue loads x while the next tile's
   // rows are already in flight (the tile kernel's epilogue loads stall its block)
-  const bool add2 = addend2.has_value() && addend2->defined();
-  const bool amask = addend_mask.has_value() && addend_mask->defined();
-  const bool stream_ok = b_kmajor && !add2 && (!amask || add) &&
-                         (!add || (addend->stride(0) > 0 && addend->stride(0) % 8 == 0 &&
-                                   (int64_t)M * addend->stride(0) * 2 < (int64_t(1) << 31)));
-  const int srows = stream_ok ? gemm_stream_rows(M, N, K, A.stride(0), C.stride(0), b_kmajor, add, true) : 0;
+  const int srows = o.stream_ok && b_kmajor
+                        ? gemm_stream_rows(M, N, K, A.stride(0), C.stride(0), b_kmajor, o.add != nullptr, true) : 0;
   if (srows > 0) {
-    const BnBwdArgs sb = make_bn_bwd(x_bn, ws, mask, mode, M, N, srows, part);
+    const BnBwdArgs sb = make_bn_bwd("gemm_nt_bn", x_bn, ws, mask, mode, M, N, srows, part);
     if (launch_gemm_stream(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), b_kmajor, C.data_ptr(), C.stride(0), M,
-                           N, K, nullptr, current_stream(A), add ? addend->data_ptr() : nullptr,
-                           add ? addend->stride(0) : 0, addend_mask_ptr(addend_mask, M, N, add), &sb))
+                           N, K, nullptr, current_stream(A), o.add, o.ld_add, o.add_mask, &sb))
       return {C, part};
   }
-  const BnBwdArgs bnb = make_bn_bwd(x_bn, ws, mask, mode, M, N, gemm_nt_stats_rows(M, N, kTileAuto, K, false), part);
+  const BnBwdArgs bnb =
+      make_bn_bwd("gemm_nt_bn", x_bn, ws, mask, mode, M, N, gemm_nt_stats_rows(M, N, kTileAuto, K, false), part);
   launch_gemm_nt(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0), M, N, K, nullptr,
-                 current_stream(A), add ? addend->data_ptr() : nullptr, add ? addend->stride(0) : 0, b_kmajor,
-                 kTileAuto, &bnb, addend_mask_ptr(addend_mask, M, N, add), addend2_ptr(addend2, M, N, H, W), (int)H,
-                 (int)W);
+                 current_stream(A), o.add, o.ld_add, b_kmajor, kTileAuto, &bnb, o.add_mask, o.add2, (int)H, (int)W);
   return {C, part};
 }
 
@@ -779,7 +777,7 @@ at::Tensor conv_f32_fwd(at::Tensor x, at::Tensor w, int64_t pad, int64_t stride,
   TORCH_CHECK(conv_f32_supported(C, Cout, (int64_t)N * OH * OW, R * S * C),
               "conv_f32_fwd: needs C % 4 == 0, Cout % 4 == 0 and fewer than 2^24 output pixels");
   at::Tensor y;
-  if (out.has_value() && out->defined()) {
+  if (opt(out)) {
     y = *out;
     check_nhwc_f32(y, "conv_f32_fwd out");
     TORCH_CHECK(y.size(0) == N && y.size(1) == Cout && y.size(2) == OH && y.size(3) == OW, "conv_f32_fwd: out shape");
@@ -787,7 +785,7 @@ at::Tensor conv_f32_fwd(at::Tensor x, at::Tensor w, int64_t pad, int64_t stride,
     y = at::empty({N, Cout, OH, OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   }
   launch_conv_f32_fwd(x.data_ptr<float>(), ldx, N, H, W, C, w.data_ptr<float>(), Cout, R, S, (int)pad, (int)stride,
-                      y.data_ptr<float>(), out.has_value() && out->defined(), current_stream(x));
+                      y.data_ptr<float>(), opt(out) != nullptr, current_stream(x));
   return y;
 }
 
@@ -814,13 +812,13 @@ at::Tensor gemm_tn(at::Tensor A, at::Tensor B, c10::ScalarType out_dtype, double
   check_mat(A, "A");
   check_mat(B, "B");
   TORCH_CHECK(A.size(0) == B.size(0), "gemm_tn: K mismatch");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16, "gemm_tn: fp32/bf16 output");
+  const int out_code = out_dtype_code(out_dtype, "gemm_tn");
   const int K = (int)A.size(0), Mo = (int)A.size(1), No = (int)B.size(1);
   at::Tensor out = at::empty({Mo, No}, A.options().dtype(out_dtype));
   const int splits = gemm_tn_splits(Mo, No, K);
   at::Tensor part = at::empty({(int64_t)splits * Mo * No}, A.options().dtype(at::kFloat));
   launch_gemm_tn(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), part.data_ptr<float>(), splits, Mo, No, K,
-                 out.data_ptr(), out_dtype == at::kFloat ? kF32 : kBF16, (float)scale, false, current_stream(A));
+                 out.data_ptr(), out_code, (float)scale, false, current_stream(A));
   return out;
 }
 
@@ -837,32 +835,30 @@ std::vector<at::Tensor> conv1x1_dual(at::Tensor dy, at::Tensor x, at::Tensor w, 
   TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.scalar_type() == at::kBFloat16 && w.is_contiguous(),
               "conv1x1_dual: w must be a contiguous bf16 [Cout, Cin] matrix");
   TORCH_CHECK(dy.size(0) == x.size(0) && w.size(0) == dy.size(1) && w.size(1) == x.size(1), "conv1x1_dual: shapes");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16, "conv1x1_dual: fp32/bf16 weight gradient");
+  const int out_code = out_dtype_code(out_dtype, "conv1x1_dual");
   const int64_t M = dy.size(0);
   const int Cout = (int)dy.size(1), Cin = (int)x.size(1);
   const int groups = conv1x1_dual_groups(M, Cin, Cout);
   if (!groups || dy.stride(0) != Cout || x.stride(0) != Cin) return {};
-  const bool bn = y_bn.has_value() && y_bn->defined();
+  const bool bn = opt(y_bn) != nullptr;
+  const float* wp = nullptr;
+  const uint8_t* mp = nullptr;
   if (bn) {
     if (!conv1x1_dual_bn_ok(M, Cin, Cout)) return {};
     check_mat(*y_bn, "y_bn");
     TORCH_CHECK(y_bn->sizes() == dy.sizes() && y_bn->stride(0) == Cout, "conv1x1_dual: y_bn must be laid out like dy");
-    TORCH_CHECK(ws.has_value() && ws->scalar_type() == at::kFloat && ws->is_contiguous() && ws->numel() == 7 * Cout,
-                "conv1x1_dual: ws must be the BN's finalized 7C workspace");
-    TORCH_CHECK(mask.has_value() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
-                    mask->numel() * 8 >= M * Cout,
-                "conv1x1_dual: the BN's 1-bit ReLU mask");
+    TORCH_CHECK(opt(ws) && opt(mask), "conv1x1_dual: y_bn needs the BN's finalized ws and its 1-bit ReLU mask");
+    wp = check_ws(*ws, Cout, "conv1x1_dual", "ws");
+    mp = check_bitmask(*mask, M * Cout, "conv1x1_dual", "mask");
   }
   at::Tensor dx = at::empty({M, Cin}, dy.options());
   at::Tensor part = at::empty({(int64_t)groups * Cout * Cin}, dy.options().dtype(at::kFloat));
   at::Tensor dw = at::empty({Cout, Cin}, dy.options().dtype(out_dtype));
   hipStream_t st = current_stream(dy);
   TORCH_CHECK(launch_conv1x1_dual(dy.data_ptr(), x.data_ptr(), w.data_ptr(), dx.data_ptr(), part.data_ptr<float>(), M,
-                                  Cin, Cout, st, bn ? y_bn->data_ptr() : nullptr,
-                                  bn ? mask->data_ptr<uint8_t>() : nullptr, bn ? ws->data_ptr<float>() : nullptr),
+                                  Cin, Cout, st, bn ? y_bn->data_ptr() : nullptr, mp, wp),
               "conv1x1_dual: kernel refused a shape it planned");
-  launch_splitk_reduce(part.data_ptr<float>(), groups, (int64_t)Cout * Cin, dw.data_ptr(),
-                       out_dtype == at::kFloat ? kF32 : kBF16, 1.f, false, st);
+  launch_splitk_reduce(part.data_ptr<float>(), groups, (int64_t)Cout * Cin, dw.data_ptr(), out_code, 1.f, false, st);
   return {dx, dw};
 }
 
@@ -884,23 +880,9 @@ std::vector<at::Tensor> bn_relu_maxpool_fwd(at::Tensor x, c10::optional<at::Tens
   // ceil mode (GoogLeNet) only adds trailing windows that start inside the input; the kernels skip
   // their out-of-range taps and the backward gather clamps to OH/OW
   const int OH = pool_out(H, (int)k, (int)s, (int)p, ceil_mode), OW = pool_out(W, (int)k, (int)s, (int)p, ceil_mode);
-  auto f32 = x.options().dtype(at::kFloat);
-  auto fptr = [](const c10::optional<at::Tensor>& t) -> float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "BN parameters/stats must be fp32 contiguous");
-    return t->data_ptr<float>();
-  };
-  at::Tensor ws = at::empty({7 * (int64_t)C}, f32);
-  const bool ext = stats.has_value() && stats->defined();
-  if (ext) {
-    TORCH_CHECK(stats->scalar_type() == at::kFloat && stats->is_contiguous() && stats->dim() == 3 &&
-                    stats->size(1) == C && stats->size(2) == 2,
-                "stats must be fp32 [row_blocks, C, 2] partials");
-  }
-  at::Tensor part = at::empty({ext ? ext_part_floats(stats, C) : partial_floats(M, C)}, f32);
-  launch_bn_fwd(x.data_ptr(), nullptr, nullptr, M, C, kBF16, fptr(weight), fptr(bias), (float)eps, (float)momentum,
-                fptr(running_mean), fptr(running_var), ws.data_ptr<float>(), part.data_ptr<float>(), true, true,
-                current_stream(x), ext ? stats->data_ptr<float>() : nullptr, ext ? (int)stats->size(0) : 0);
+  at::Tensor ws = at::empty({7 * (int64_t)C}, x.options().dtype(at::kFloat));
+  bn_forward("bn_relu_maxpool_fwd", x, nullptr, nullptr, weight, bias, running_mean, running_var, momentum, eps, ws, true,
+             true, stats);
   auto opts = x.options().memory_format(at::MemoryFormat::ChannelsLast);
   at::Tensor y = at::empty({N, C, OH, OW}, opts);
   at::Tensor pos = at::empty({N, C, OH, OW}, opts.dtype(at::kByte));
@@ -915,9 +897,9 @@ std::vector<at::Tensor> bn_relu_maxpool_bwd(at::Tensor dy_pool, at::Tensor pos, 
                                             bool want_dx) {
   dy_pool = dy_pool.contiguous(at::MemoryFormat::ChannelsLast).to(at::kBFloat16);
   check_act(x, "x");
-  TORCH_CHECK(pos.scalar_type() == at::kByte && pos.sizes() == dy_pool.sizes() &&
-                  pos.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "bn_relu_maxpool_bwd: pos must be the forward's positions");
+  TORCH_CHECK(dy_pool.is_cuda() && x.dim() == 4 && dy_pool.size(0) == x.size(0) && dy_pool.size(1) == x.size(1),
+              "bn_relu_maxpool_bwd: dy_pool must be the GPU gradient of x's pooled output");
+  const uint8_t* pp = check_pos(pos, dy_pool, "bn_relu_maxpool_bwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
   const int OH = (int)dy_pool.size(2), OW = (int)dy_pool.size(3);
   const int64_t M = (int64_t)N * H * W;
@@ -930,11 +912,10 @@ std::vector<at::Tensor> bn_relu_maxpool_bwd(at::Tensor dy_pool, at::Tensor pos, 
               "bn_relu_maxpool_bwd: want_dx=False needs the quad form (3x3 / stride 2, even input)");
   at::Tensor dx = want_dx ? at::empty_like(x) : at::Tensor();
   at::Tensor dg = at::empty({C}, f32), db = at::empty({C}, f32);
-  const float* g = (weight.has_value() && weight->defined()) ? weight->data_ptr<float>() : nullptr;
-  launch_bn_relu_maxpool_bwd(dy_pool.data_ptr(), pos.data_ptr<uint8_t>(), x.data_ptr(),
-                             want_dx ? dx.data_ptr() : nullptr, N, H, W, C, OH,
-                             OW, (int)k, (int)s, (int)p, g, ws.data_ptr<float>(), part.data_ptr<float>(),
-                             dg.data_ptr<float>(), db.data_ptr<float>(), current_stream(x));
+  launch_bn_relu_maxpool_bwd(dy_pool.data_ptr(), pp, x.data_ptr(), want_dx ? dx.data_ptr() : nullptr, N, H, W, C, OH, OW,
+                             (int)k, (int)s, (int)p, f32_vec(weight, C, "bn_relu_maxpool_bwd", "weight"),
+                             check_ws(ws, C, "bn_relu_maxpool_bwd", "ws"), part.data_ptr<float>(), dg.data_ptr<float>(),
+                             db.data_ptr<float>(), current_stream(x));
   return {dx, dg, db};
 }
 
@@ -966,12 +947,10 @@ std::vector<at::Tensor> maxpool_fwd(at::Tensor x, int64_t k, int64_t s, int64_t 
 at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor pos, int64_t H, int64_t W, int64_t k, int64_t s, int64_t p) {
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   check_act(dy, "dy");
-  TORCH_CHECK(pos.scalar_type() == at::kByte && pos.sizes() == dy.sizes() &&
-                  pos.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "maxpool_bwd: pos must be the forward's uint8 positions");
+  const uint8_t* pp = check_pos(pos, dy, "maxpool_bwd");
   const int N = (int)dy.size(0), C = (int)dy.size(1), OH = (int)dy.size(2), OW = (int)dy.size(3);
   at::Tensor dx = at::empty({N, C, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  launch_maxpool_bwd(dy.data_ptr(), pos.data_ptr<uint8_t>(), dx.data_ptr(), N, (int)H, (int)W, C, OH, OW, (int)k,
+  launch_maxpool_bwd(dy.data_ptr(), pp, dx.data_ptr(), N, (int)H, (int)W, C, OH, OW, (int)k,
                      (int)s, (int)p, dtype_code(dy), current_stream(dy));
   return dx;
 }
@@ -1005,42 +984,34 @@ std::vector<at::Tensor> stem_fwd(at::Tensor x, at::Tensor wpk, bool want_stats) 
 // bn_relu_maxpool_bwd(..., want_dx=False) finalized. The conv output's gradient is never materialised.
 at::Tensor stem_wgrad_bn(at::Tensor dy_pool, at::Tensor pos, at::Tensor x, at::Tensor ws, at::Tensor xs, int64_t H,
                          int64_t W, c10::ScalarType out_dtype) {
+  const int out_code = out_dtype_code(out_dtype, "stem_wgrad_bn");
   dy_pool = dy_pool.contiguous(at::MemoryFormat::ChannelsLast).to(at::kBFloat16);
   check_act(x, "x");
   check_act(dy_pool, "dy_pool");
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 4, "stem_wgrad_bn: x must be the bf16 conv output");
-  TORCH_CHECK(pos.scalar_type() == at::kByte && pos.sizes() == dy_pool.sizes() &&
-                  pos.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "stem_wgrad_bn: pos must be the pooled op's positions");
-  TORCH_CHECK(xs.is_cuda() && xs.dim() == 4 && xs.size(3) == 16 && xs.scalar_type() == at::kBFloat16 &&
-                  xs.is_contiguous(),
-              "stem_wgrad_bn: xs must be the forward's folded [N, OH, OW, 16] input");
+  const uint8_t* pp = check_pos(pos, dy_pool, "stem_wgrad_bn");
+  check_stem_fold(xs, "stem_wgrad_bn");
   const int N = (int)x.size(0), Cout = (int)x.size(1), OH = (int)dy_pool.size(2), OW = (int)dy_pool.size(3);
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() == 7 * (int64_t)Cout,
-              "stem_wgrad_bn: ws must be the 7C workspace");
+  float* wp = check_ws(ws, Cout, "stem_wgrad_bn", "ws");
   TORCH_CHECK(xs.size(0) == N && xs.size(1) == (H + 1) / 2 && xs.size(2) == (W + 1) / 2 && x.size(2) == xs.size(1) &&
                   x.size(3) == xs.size(2) && dy_pool.size(0) == N && dy_pool.size(1) == Cout,
               "stem_wgrad_bn: x / xs / dy_pool / image size mismatch");
   TORCH_CHECK(stem_wgrad_bn_eligible(N, (int)H, (int)W, Cout, OH, OW),
               "stem_wgrad_bn: needs 64 channels, an even conv output and a 3x3 / s2 / p1 pool");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16, "stem_wgrad_bn: fp32/bf16 output");
   const int splits = stem_wgrad_bn_splits(N, (int)H, (int)W);
   at::Tensor part = at::empty({(int64_t)splits * Cout * 256}, xs.options().dtype(at::kFloat));
   at::Tensor dw = at::empty({Cout, 256}, xs.options().dtype(out_dtype));
-  launch_stem_wgrad_bn(dy_pool.data_ptr(), pos.data_ptr<uint8_t>(), x.data_ptr(), ws.data_ptr<float>(), xs.data_ptr(),
-                       part.data_ptr<float>(), splits, dw.data_ptr(), out_dtype == at::kFloat ? kF32 : kBF16, N,
-                       (int)H, (int)W, OH, OW, current_stream(xs));
+  launch_stem_wgrad_bn(dy_pool.data_ptr(), pp, x.data_ptr(), wp, xs.data_ptr(), part.data_ptr<float>(), splits,
+                       dw.data_ptr(), out_code, N, (int)H, (int)W, OH, OW, current_stream(xs));
   return dw;
 }
 
 at::Tensor stem_wgrad(at::Tensor dy, at::Tensor xs, int64_t H, int64_t W, c10::ScalarType out_dtype) {
+  const int out_code = out_dtype_code(out_dtype, "stem_wgrad");
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  TORCH_CHECK(xs.is_cuda() && xs.dim() == 4 && xs.size(3) == 16 && xs.scalar_type() == at::kBFloat16 &&
-                  xs.is_contiguous(),
-              "stem_wgrad: xs must be the forward's folded [N, OH, OW, 16] input");
+  check_stem_fold(xs, "stem_wgrad");
   check_act(dy, "dy");
   TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.size(1) % 64 == 0, "stem_wgrad: dy must be bf16, Cout % 64");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16, "stem_wgrad: fp32/bf16 output");
   const int N = (int)xs.size(0), Cout = (int)dy.size(1);
   TORCH_CHECK(xs.size(1) == (H + 1) / 2 && xs.size(2) == (W + 1) / 2, "stem_wgrad: xs / image size mismatch");
   TORCH_CHECK((int64_t)N * xs.size(1) * xs.size(2) < (1 << 24), "stem_wgrad: too many output pixels");
@@ -1048,8 +1019,8 @@ at::Tensor stem_wgrad(at::Tensor dy, at::Tensor xs, int64_t H, int64_t W, c10::S
   const int splits = stem_wgrad_splits(N, (int)H, (int)W, Cout);
   at::Tensor part = at::empty({(int64_t)splits * Cout * 256}, xs.options().dtype(at::kFloat));
   at::Tensor dw = at::empty({Cout, 256}, xs.options().dtype(out_dtype));
-  launch_stem_wgrad(dy.data_ptr(), xs.data_ptr(), part.data_ptr<float>(), splits, dw.data_ptr(),
-                    out_dtype == at::kFloat ? kF32 : kBF16, N, (int)H, (int)W, Cout, current_stream(xs));
+  launch_stem_wgrad(dy.data_ptr(), xs.data_ptr(), part.data_ptr<float>(), splits, dw.data_ptr(), out_code, N, (int)H,
+                    (int)W, Cout, current_stream(xs));
   return dw;
 }
 
@@ -1123,25 +1094,37 @@ std::vector<at::Tensor> conv3x3_fwd(at::Tensor x, at::Tensor w, int64_t stride, 
   return {y, S};
 }
 
+// What the three data gradients share: dy made channels_last and checked against w, dx [N, Cin, H, W] (dy's own
+// H, W when not given) allocated and checked like a forward's input.
+static at::Tensor dgrad_dx(const char* op, at::Tensor& dy, const at::Tensor& w, int64_t H = 0, int64_t W = 0) {
+  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(dy.dim() == 4 && w.dim() == 4 && dy.size(1) == w.size(0), op, ": dy/w mismatch");
+  at::Tensor dx = at::empty({dy.size(0), w.size(1), H ? H : dy.size(2), W ? W : dy.size(3)},
+                            dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+  check_conv3(dx, w);
+  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && (reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0, op,
+              ": bf16 aligned dy");
+  return dx;
+}
+
+// the optional addend fused into a stride-1 data gradient's epilogue
+static const void* dgrad_addend(const char* op, const c10::optional<at::Tensor>& addend, const at::Tensor& dx) {
+  const at::Tensor* a = opt(addend);
+  if (!a) return nullptr;
+  TORCH_CHECK(a->is_cuda() && a->sizes() == dx.sizes() && a->scalar_type() == at::kBFloat16 &&
+                  a->is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": addend must match dx");
+  return a->data_ptr();
+}
+
 // stride-1 data gradient (+ optional fused addend, same shape as dx)
 at::Tensor conv3x3_dgrad(at::Tensor dy, at::Tensor w, c10::optional<at::Tensor> addend, int64_t tile) {
-  TORCH_CHECK(tile >= 0 && tile <= kTile512x128, "conv3x3: tile config 0..9");
-  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  TORCH_CHECK(dy.dim() == 4 && dy.size(1) == w.size(0), "conv3x3_dgrad: dy/w mismatch");
+  TORCH_CHECK(tile >= 0 && tile <= kTile512x128, "conv3x3_dgrad: tile config 0..9");
+  at::Tensor dx = dgrad_dx("conv3x3_dgrad", dy, w);
   const int N = (int)dy.size(0), Cout = (int)w.size(0), Cin = (int)w.size(1), H = (int)dy.size(2), W = (int)dy.size(3);
-  at::Tensor dx = at::empty({N, Cin, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  check_conv3(dx, w);
   TORCH_CHECK(Cout % 64 == 0 || tile_bm(tile) * tile_bn(tile) <= 128 * 128,
               "conv3x3_dgrad: Cout % 64 != 0 needs a tile of at most 128x128");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && (reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0,
-              "conv3x3_dgrad: bf16 aligned dy");
-  const void* add = nullptr;
-  if (addend.has_value() && addend->defined()) {
-    TORCH_CHECK(addend->sizes() == dx.sizes() && addend->scalar_type() == at::kBFloat16 &&
-                    addend->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv3x3_dgrad: addend must match dx");
-    add = addend->data_ptr();
-  }
+  const void* add = dgrad_addend("conv3x3_dgrad", addend, dx);
   if (tile == 0 && halo_conv_eligible(Cout, Cin, W, 1, false)) {
     // stride-1 data gradient = the forward conv of dy with W'[ci][kh][kw][co] = W[co][2-kh][2-kw][ci]
     const at::Tensor wt = w.flip({2, 3}).transpose(0, 1).contiguous(at::MemoryFormat::ChannelsLast);
@@ -1155,16 +1138,11 @@ at::Tensor conv3x3_dgrad(at::Tensor dy, at::Tensor w, c10::optional<at::Tensor> 
 
 // stride-2 3x3 data gradient for an input of even size H x W
 at::Tensor conv3x3s2_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W) {
-  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  TORCH_CHECK(dy.dim() == 4 && dy.size(1) == w.size(0), "conv3x3s2_dgrad: dy/w mismatch");
-  TORCH_CHECK(H % 2 == 0 && W % 2 == 0 && dy.size(2) == H / 2 && dy.size(3) == W / 2,
+  TORCH_CHECK(dy.dim() == 4 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && dy.size(2) == H / 2 && dy.size(3) == W / 2,
               "conv3x3s2_dgrad: needs even H, W and dy = [N, Cout, H/2, W/2]");
+  at::Tensor dx = dgrad_dx("conv3x3s2_dgrad", dy, w, H, W);
   const int N = (int)dy.size(0), Cout = (int)w.size(0), Cin = (int)w.size(1);
-  at::Tensor dx = at::empty({N, Cin, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  check_conv3(dx, w);
   TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "conv3x3s2_dgrad: Cin and Cout must be multiples of 64");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && (reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0,
-              "conv3x3s2_dgrad: bf16 aligned dy");
   launch_conv3x3s2_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), N, (int)H, (int)W, Cin, Cout,
                          current_stream(dy));
   return dx;
@@ -1173,23 +1151,13 @@ at::Tensor conv3x3s2_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W) {
 // stride-1 3x3 data gradient that is the dy of a fused BN: returns (dx, BN-backward partials)
 std::vector<at::Tensor> conv3x3_dgrad_bn(at::Tensor dy, at::Tensor w, c10::optional<at::Tensor> addend,
                                          at::Tensor x_bn, at::Tensor ws, c10::optional<at::Tensor> mask, int64_t mode) {
-  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  TORCH_CHECK(dy.dim() == 4 && dy.size(1) == w.size(0), "conv3x3_dgrad_bn: dy/w mismatch");
+  at::Tensor dx = dgrad_dx("conv3x3_dgrad_bn", dy, w);
   const int N = (int)dy.size(0), Cout = (int)w.size(0), Cin = (int)w.size(1), H = (int)dy.size(2), W = (int)dy.size(3);
-  at::Tensor dx = at::empty({N, Cin, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  check_conv3(dx, w);
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && (reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0,
-              "conv3x3_dgrad_bn: bf16 aligned dy");
-  const void* add = nullptr;
-  if (addend.has_value() && addend->defined()) {
-    TORCH_CHECK(addend->sizes() == dx.sizes() && addend->scalar_type() == at::kBFloat16 &&
-                    addend->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv3x3_dgrad_bn: addend must match dx");
-    add = addend->data_ptr();
-  }
+  const void* add = dgrad_addend("conv3x3_dgrad_bn", addend, dx);
   const int64_t P = (int64_t)N * H * W;
   at::Tensor part;
-  const BnBwdArgs bnb = make_bn_bwd(x_bn, ws, mask, mode, P, Cin, conv3x3_stats_rows(P, Cin, kTileAuto, 9 * Cout, Cout % 64 == 0), part);
+  const BnBwdArgs bnb = make_bn_bwd("conv3x3_dgrad_bn", x_bn, ws, mask, mode, P, Cin,
+                                    conv3x3_stats_rows(P, Cin, kTileAuto, 9 * Cout, Cout % 64 == 0), part);
   launch_conv3x3_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), N, H, W, Cin, Cout, add, current_stream(dy),
                        kTileAuto, &bnb);
   return {dx, part};
@@ -1197,12 +1165,13 @@ std::vector<at::Tensor> conv3x3_dgrad_bn(at::Tensor dy, at::Tensor w, c10::optio
 
 // weight gradient, returned as a channels_last [Cout, Cin, 3, 3] tensor of out_dtype
 at::Tensor conv3x3_wgrad(at::Tensor dy, at::Tensor x, int64_t stride, c10::ScalarType out_dtype) {
+  const int out_code = out_dtype_code(out_dtype, "conv3x3_wgrad");
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kBFloat16 &&
                   x.is_contiguous(at::MemoryFormat::ChannelsLast) && x.size(1) % 8 == 0,
               "conv3x3_wgrad: x must be bf16 channels_last with Cin % 8 == 0");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.size(1) % 8 == 0, "conv3x3_wgrad: dy must be bf16, Cout % 8");
-  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == at::kBFloat16, "conv3x3_wgrad: fp32/bf16 output");
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 && dy.size(1) % 8 == 0,
+              "conv3x3_wgrad: dy must be a bf16 GPU tensor, Cout % 8");
   TORCH_CHECK(x.numel() / x.size(1) < (1 << 24), "conv3x3_wgrad: too many pixels");
   const int N = (int)x.size(0), Cin = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), Cout = (int)dy.size(1);
   TORCH_CHECK(dy.size(2) == (H - 1) / stride + 1 && dy.size(3) == (W - 1) / stride + 1, "conv3x3_wgrad: dy shape");
@@ -1210,14 +1179,14 @@ at::Tensor conv3x3_wgrad(at::Tensor dy, at::Tensor x, int64_t stride, c10::Scala
   if (halo_wgrad_eligible(Cin, Cout, W, (int)stride) && (int64_t)N * (H + 2) * (W + 2) < (1 << 30)) {
     const int hs = halo_wgrad_splits(N, H, W);
     at::Tensor hpart = at::empty({(int64_t)hs * Cout * 9 * Cin}, x.options().dtype(at::kFloat));
-    launch_conv3x3_halo_wgrad(dy.data_ptr(), x.data_ptr(), hpart.data_ptr<float>(), hs, dw.data_ptr(),
-                              out_dtype == at::kFloat ? kF32 : kBF16, N, H, W, current_stream(x));
+    launch_conv3x3_halo_wgrad(dy.data_ptr(), x.data_ptr(), hpart.data_ptr<float>(), hs, dw.data_ptr(), out_code, N, H, W,
+                              current_stream(x));
     return dw;
   }
   const int splits = conv3x3_wgrad_splits(N, H, W, Cin, Cout, (int)stride);
   at::Tensor part = at::empty({(int64_t)splits * Cout * 9 * Cin}, x.options().dtype(at::kFloat));
-  launch_conv3x3_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), splits, dw.data_ptr(),
-                       out_dtype == at::kFloat ? kF32 : kBF16, N, H, W, Cin, Cout, (int)stride, current_stream(x));
+  launch_conv3x3_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), splits, dw.data_ptr(), out_code, N, H, W,
+                       Cin, Cout, (int)stride, current_stream(x));
   return dw;
 }
 
@@ -1305,8 +1274,11 @@ void bind_nn(pybind11::module& m) {
         pybind11::arg("H") = 0, pybind11::arg("W") = 0);
   m.def("gemm_nt_splitk_splits", [](int64_t M, int64_t N, int64_t K) { return gemm_nt_splitk_splits((int)M, (int)N, (int)K); },
         "split count gemm_nt uses for this shape (1 = tile kernel)");
-  m.def("pick_tile", [](int64_t M, int64_t N, int64_t K, bool wide_ok) { return pick_tile(M, (int)N, kTileAuto, (int)K, wide_ok); },
-        "tile config the auto policy picks for an M x N GEMM with reduction K (TileCfg: 1 = 128x128, 2 = 128x64, 8 = 256x256)");
+  m.def("pick_tile", [](int64_t M, int64_t N, int64_t K, bool wide_ok, bool stats) {
+        return pick_tile(M, (int)N, kTileAuto, (int)K, wide_ok, stats); },
+        "tile config the auto policy picks for an M x N GEMM with reduction K (TileCfg: 1 = 128x128, 2 = 128x64, 8 = 256x256); "
+        "stats: a forward with the BN-statistics epilogue and no addend",
+        pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("wide_ok"), pybind11::arg("stats") = false);
   m.def("pick_conv_tile", [](int64_t P, int64_t N, int64_t K, bool wide_ok) { return pick_conv_tile(P, (int)N, kTileAuto, (int)K, wide_ok); },
         "tile of a 3x3 forward / data-gradient launch (pick_tile + the conv-only 512x128 tile)");
   m.def("gemm_tn_splits", [](int64_t Mo, int64_t No, int64_t K) { return gemm_tn_splits((int)Mo, (int)No, (int)K); },

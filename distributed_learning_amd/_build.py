@@ -173,21 +173,24 @@ SANITIZE_DIR = ROOT / "build" / "sanitize"
 
 
 def sanitize_check(run: bool = True) -> int:
-    """CPU AddressSanitizer + UndefinedBehaviorSanitizer build of the comm engine's host C++ (plan builder,
-    virtual-rank host executor, IPC host protocol; csrc/tests/host_check.cpp) -- the GPU pool runs no
-    sanitizers, so this is where they apply. Returns the check's exit status (0 = clean)."""
+    """CPU AddressSanitizer + UndefinedBehaviorSanitizer builds of the host C++ that needs no GPU: the comm engine
+    (plan builder, virtual-rank host executor, IPC host protocol; csrc/tests/host_check.cpp) and the environment
+    switch type (csrc/include/dla_knob.h; csrc/tests/knob_check.cpp) -- the GPU pool runs no sanitizers, so this
+    is where they apply. Returns the first non-zero exit status of the checks (0 = all clean)."""
     SANITIZE_DIR.mkdir(parents=True, exist_ok=True)
-    exe = SANITIZE_DIR / "host_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer", "-pthread", str(CSRC / "tests" / "host_check.cpp"), str(CSRC / "comm" / "plan.cpp"),
-           "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
-    if not run:
-        return 0
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    return subprocess.run([str(exe)], env=env).returncode
+    for name, extra in (("host_check", [CSRC / "comm" / "plan.cpp"]), ("knob_check", [])):
+        exe = SANITIZE_DIR / name
+        cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+               "-fno-omit-frame-pointer", "-pthread", str(CSRC / "tests" / f"{name}.cpp"), *map(str, extra), "-o", str(exe)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"sanitizer build of {name} failed:\n{r.stdout}\n{r.stderr}")
+        if run:
+            rc = subprocess.run([str(exe)], env=env).returncode
+            if rc != 0:
+                return rc
+    return 0
 
 
 def main(argv=None):
@@ -198,7 +201,7 @@ def main(argv=None):
     ap.add_argument("-D", "--define", action="append", default=[], help="extra -D for a variant build")
     ap.add_argument("--out", default=None, help="output .so (variant builds)")
     ap.add_argument("--sanitize", action="store_true",
-                    help="build and run the ASan/UBSan CPU check of the host-side comm C++ instead")
+                    help="build and run the ASan/UBSan CPU checks of the host-side C++ instead")
     a = ap.parse_args(argv)
     if a.sanitize:
         return sanitize_check()

@@ -1,8 +1,9 @@
 """Every environment switch of the framework, in one table, read in one place.
 
 Each knob is the environment variable ``DLA_<NAME>``. Python reads it only through :func:`get`
-(parsed once, cached); the C++/HIP side reads its own (``std::getenv`` once per process, in the
-file named in the table) and the table documents those too, so :func:`non_default` reports every
+(parsed once, cached); the C++/HIP side reads its own (each one declaration of
+``csrc/include/dla_knob.h``'s type, in the file named in the table, read once per process) and the table
+documents those too -- tests/test_knobs.py holds names, defaults and files to the declarations -- so :func:`non_default` reports every
 switch a run was started with. ``bench.py`` records ``non_default()`` as ``"knobs"`` in its JSON
 line: ``{}`` means the shipped defaults, the only combination the end-to-end tests and the credited
 numbers use. Defaults are the measured-best settings; the alternatives stay for A/B runs
