@@ -270,6 +270,11 @@ void launch_maxpool_fwd(const void* x, void* y, uint8_t* pos, int N, int H, int 
                         int s, int p, int dtype, hipStream_t stream);
 void launch_maxpool_bwd(const void* dy, const uint8_t* pos, void* dx, int N, int H, int W, int C, int OH, int OW,
                         int k, int s, int p, int dtype, hipStream_t stream);
+// whether a pool kernel over `work` flat indices with index divisors d0, d1, d2 decodes them by multiply-shift
+// (mm::FastDiv's exact domain: work < 2^24 and every divisor < 2^16) or by hardware division
+bool pool_fast_index(int64_t work, int64_t d0, int64_t d1, int64_t d2);
+void set_pool3_sep(int rows);  // 3x3/s1 forward: 4 / 7-row separable strips, 0 generic kernel, -1 DLA_POOL3_SEP / 4
+int pool3_strip_rows();        // the strip height in force (0: the generic kernel)
 // global average pooling over the H*W pixels of NHWC x: y [N, C]; backward dx [N, H, W, C] = dy / HW
 void launch_gap_fwd(const void* x, void* y, int N, int HW, int C, int dtype, hipStream_t stream);
 // y [N, H/2, W/2, C] = x [N, H, W, C] at even (h, w); bf16 NHWC, C % 8 == 0

@@ -23,7 +23,11 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
-// n / d for n < 2^24, d < 2^16: floor(n * ceil(2^40 / d) / 2^40), 4 VALU ops.
+// n / d for n < 2^24, d < 2^16: floor(n * ceil(2^40 / d) / 2^40), 4 VALU ops. Domain: BOTH bounds. With
+// m = ceil(2^40 / d), m d = 2^40 + r and 0 <= r < d, so n m / 2^40 = n / d + n r / (d 2^40): the overshoot is below
+// n / 2^40 < 2^-16, and it must stay below 1 / d (the distance of n / d from the next integer), which it does only
+// while d <= 2^16. Past it the quotient can come out one too large (d = 1048577, n = d - 1 gives 1, not 0); a caller
+// that cannot bound its divisors divides in hardware instead (pool.hip pool_fast_index, conv_halo.hip).
 struct FastDiv {
   uint32_t d, m_lo, m_hi;
 };

@@ -28,7 +28,7 @@ struct PoolGeom {
 };
 
 // Flat index t -> (n, row, col, channel) of an [N, rows, cols, C] NHWC tensor in 8-channel groups.
-// kFast: multiply-shift division (t < 2^24, host-checked), else hardware integer division.
+// kFast: multiply-shift division (host-checked: pool_fast_index), else hardware integer division.
 template <bool kFast>
 __device__ __forceinline__ void decode(int t, const PoolGeom& g, int cols, int rows, int& n, int& row, int& col,
                                        int& c) {
@@ -284,6 +284,23 @@ __global__ __launch_bounds__(kPoolThreads) void maxpool_bwd_kernel(const T* __re
   }
 }
 
+// mm::FastDiv's domain: mm::fdiv(n, d) is floor(n / d) only for n < 2^24 AND d < 2^16. Every dividend of decode()
+// is at most the flat index (< work) and its divisors are d0, d1, d2, so the multiply-shift instantiation is taken
+// only when all four hold; anything else (a [1, 8, 2, 1048577] image has 2^20 work items but a 2^20 + 1 divisor,
+// whose quotient at n = d - 1 comes out 1) runs the hardware-division one.
+bool pool_fast_index(int64_t work, int64_t d0, int64_t d1, int64_t d2) {
+  return work < (1 << 24) && std::max(d0, std::max(d1, d2)) < (1 << 16);
+}
+
+// 3x3/s1 forward: separable strips of 4 output rows (DLA_POOL3_SEP / set_pool3_sep: 7 = strips of 7, anything else
+// = the generic K = 3 kernel; A/B runs and tests)
+static Knob k_pool3_sep = Knob::integer("POOL3_SEP", 4);
+void set_pool3_sep(int rows) { k_pool3_sep.set(rows); }
+int pool3_strip_rows() {
+  const int v = k_pool3_sep.value();
+  return v == 4 || v == 7 ? v : 0;
+}
+
 static int pool_blocks(int64_t work) {
   // grid-stride: enough waves to fill 256 CUs several times over, capped to bound tail effects
   const int64_t b = (work + kPoolThreads - 1) / kPoolThreads;
@@ -296,16 +313,14 @@ void launch_maxpool_fwd(const void* x, void* y, uint8_t* pos, int N, int H, int 
   const int64_t work = (int64_t)N * OH * OW * (C / 8);
   const int nb = pool_blocks(work);
   if (nb == 0) return;
-  const bool fast = work < (1 << 24);
-  // 3x3/s1: separable strips of 4 output rows (DLA_POOL3_SEP=0: generic kernel, 7: strips of 7; A/B)
-  static Knob k_pool3_sep = Knob::integer("POOL3_SEP", 4);
-  const int sep3 = k_pool3_sep.value();
-  if (k == 3 && s == 1 && (sep3 == 4 || sep3 == 7)) {
+  const bool fast = pool_fast_index(work, C / 8, OW, OH);
+  const int sep3 = pool3_strip_rows();
+  if (k == 3 && s == 1 && sep3 != 0) {
     const int nstrip = (OH + sep3 - 1) / sep3;
     PoolGeom gs{N, H, W, C, OH, OW, k, s, p, mm::make_fastdiv(C / 8), mm::make_fastdiv(OW), mm::make_fastdiv(nstrip)};
     const int64_t swork = (int64_t)N * nstrip * OW * (C / 8);
     const int snb = pool_blocks(swork);
-    const bool sfast = swork < (1 << 24);
+    const bool sfast = pool_fast_index(swork, C / 8, OW, nstrip);
 #define DLA_MPS(T, RV, F)                                                                                         \
   hipLaunchKernelGGL((maxpool3s1_fwd_kernel<T, RV, F>), dim3(snb), dim3(kPoolThreads), 0, stream, (const T*)x, (T*)y, \
                      pos, gs, nstrip)
@@ -334,7 +349,7 @@ void launch_maxpool_bwd(const void* dy, const uint8_t* pos, void* dx, int N, int
   const int64_t work = (int64_t)N * H * W * (C / 8);
   const int nb = pool_blocks(work);
   if (nb == 0) return;
-  const bool fast = work < (1 << 24);
+  const bool fast = pool_fast_index(work, C / 8, W, H);
   const int r = (k + s - 1) / s;  // windows per axis covering one input pixel, at most
 #define DLA_MPB(T, R, F)                                                                                        \
   hipLaunchKernelGGL((maxpool_bwd_kernel<T, R, F>), dim3(nb), dim3(kPoolThreads), 0, stream, (const T*)dy, pos, \

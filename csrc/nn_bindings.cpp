@@ -877,6 +877,9 @@ std::vector<at::Tensor> bn_relu_maxpool_fwd(at::Tensor x, c10::optional<at::Tens
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
   const int64_t M = (int64_t)N * H * W;
   TORCH_CHECK(M < (1 << 24), "bn_relu_maxpool: too many pixels for 24-bit index math");
+  // the fused kernels have no hardware-division form: every divisor of their index decode (C / 8, OW, OH; W, H and
+  // W / 2, H / 2 in the backward) must stay inside mm::FastDiv's domain (dla_mfma.h)
+  TORCH_CHECK(W < 65536 && H < 65536 && C / 8 < 65536, "bn_relu_maxpool: H, W and C / 8 must be below 65536");
   // ceil mode (GoogLeNet) only adds trailing windows that start inside the input; the kernels skip
   // their out-of-range taps and the backward gather clamps to OH/OW
   const int OH = pool_out(H, (int)k, (int)s, (int)p, ceil_mode), OW = pool_out(W, (int)k, (int)s, (int)p, ceil_mode);
@@ -903,6 +906,8 @@ std::vector<at::Tensor> bn_relu_maxpool_bwd(at::Tensor dy_pool, at::Tensor pos, 
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
   const int OH = (int)dy_pool.size(2), OW = (int)dy_pool.size(3);
   const int64_t M = (int64_t)N * H * W;
+  TORCH_CHECK(M < (1 << 24) && W < 65536 && H < 65536,
+              "bn_relu_maxpool_bwd: N*H*W must be below 2^24 and H, W below 65536 (24-bit index math)");
   auto f32 = x.options().dtype(at::kFloat);
   at::Tensor part = at::empty({bn_relu_maxpool_part_floats(M, C)}, f32);
   // want_dx false: the quad reduce + finalize only (ws then holds the backward coefficients); the stem weight
@@ -945,10 +950,24 @@ std::vector<at::Tensor> maxpool_fwd(at::Tensor x, int64_t k, int64_t s, int64_t 
 }
 
 at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor pos, int64_t H, int64_t W, int64_t k, int64_t s, int64_t p) {
+  // what needs no device first: the window as the forward accepts it (s = 0 would divide by zero on the device, k > 15
+  // leaves the position byte), the image size, and dy as the pooled size of that image
+  TORCH_CHECK(dy.dim() == 4, "maxpool_bwd: dy must be 4-D");
+  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 || dy.scalar_type() == at::kFloat, "maxpool_bwd: dy must be bf16 or fp32");
+  TORCH_CHECK(k >= 1 && k <= 15 && s >= 1 && p >= 0 && 2 * p <= k, "maxpool_bwd: unsupported window");
+  TORCH_CHECK(H >= 1 && W >= 1 && H < (1LL << 30) && W < (1LL << 30), "maxpool_bwd: H and W must be positive (< 2^30)");
+  const int N = (int)dy.size(0), C = (int)dy.size(1), OH = (int)dy.size(2), OW = (int)dy.size(3);
+  const auto out_of = [&](int64_t in, int o) {
+    return o == pool_out((int)in, (int)k, (int)s, (int)p, false) || o == pool_out((int)in, (int)k, (int)s, (int)p, true);
+  };
+  TORCH_CHECK(OH > 0 && OW > 0 && out_of(H, OH) && out_of(W, OW), "maxpool_bwd: dy [", OH, ", ", OW,
+              "] is not the pooled size of an [", H, ", ", W, "] input (floor or ceil mode)");
+  const int64_t ncg = (int64_t)N * (C / 8);  // each factor is checked below 2^31 first: no int64 overflow
+  TORCH_CHECK(H * W < (1LL << 31) && ncg < (1LL << 31) && H * W * ncg < (1LL << 31),
+              "maxpool_bwd: tensor too large for 32-bit indexing");
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   check_act(dy, "dy");
   const uint8_t* pp = check_pos(pos, dy, "maxpool_bwd");
-  const int N = (int)dy.size(0), C = (int)dy.size(1), OH = (int)dy.size(2), OW = (int)dy.size(3);
   at::Tensor dx = at::empty({N, C, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
   launch_maxpool_bwd(dy.data_ptr(), pp, dx.data_ptr(), N, (int)H, (int)W, C, OH, OW, (int)k,
                      (int)s, (int)p, dtype_code(dy), current_stream(dy));
@@ -1234,6 +1253,10 @@ void bind_nn(pybind11::module& m) {
         pybind11::arg("k"), pybind11::arg("s"), pybind11::arg("p"), pybind11::arg("ceil_mode") = false,
         pybind11::arg("need_pos") = true);
   m.def("maxpool_bwd", &maxpool_bwd, "NHWC max pooling backward (gather form)");
+  m.def("set_pool3_sep", &set_pool3_sep, "3x3/s1 max-pool forward: 4 / 7-row separable strips, 0 generic kernel, -1 environment (default 4)");
+  m.def("pool3_strip_rows", &pool3_strip_rows, "strip height of the 3x3/s1 max-pool forward in force (0: generic kernel)");
+  m.def("pool_fast_index", &pool_fast_index, "whether a pool kernel over `work` indices with divisors d0, d1, d2 decodes by multiply-shift",
+        pybind11::arg("work"), pybind11::arg("d0"), pybind11::arg("d1"), pybind11::arg("d2"));
   m.def("bn_dual_fwd", &bn_dual_fwd, "training act(BN(x) + BN_d(xd)) in one apply pass (downsample residual)",
         pybind11::arg("x"), pybind11::arg("xd"), pybind11::arg("weight"), pybind11::arg("bias"),
         pybind11::arg("running_mean"), pybind11::arg("running_var"), pybind11::arg("weight_d"), pybind11::arg("bias_d"),

@@ -93,7 +93,7 @@ TABLE: Dict[str, Knob] = {
     "HALO_DIRECT_FWD": Knob("0", "csrc/kernels/conv_halo.hip", "1: the variant-2 halo forward stores its tile and "
                                                                "statistics from registers"),
     "HALO_WGRAD": Knob("1", "csrc/kernels/conv_halo_wgrad.hip", "0: implicit-GEMM 64-ch 3x3 weight gradient"),
-    "POOL3_SEP": Knob("4", "csrc/kernels/pool.hip", "separable 3x3 stride-1 max-pool variant (4 / 7; other: off; r3w/)"),
+    "POOL3_SEP": Knob("4", "csrc/kernels/pool.hip", "separable 3x3 stride-1 max-pool variant (4 / 7; other: off; r3w/; set_pool3_sep)"),
     "BN_RED_BLOCKS": Knob("1024", "csrc/kernels/bn_act.hip", "BN reduction-pass block target"),
     # ---- diagnostics -------------------------------------------------------------------------------
     "HOOK_TIMING": Knob("0", "parallel/grad_sync.py", "1: host time inside the gradient hooks"),

@@ -107,3 +107,45 @@ def test_every_tensor_op_of_bind_nn_is_covered():
 def test_host_tensors_are_refused(op):
     with pytest.raises(RuntimeError):
         CALLS[op](_ext.require())
+
+
+# ---- maxpool_bwd: window, image size and dy's size are checked from the arguments alone, before the device check,
+# so host tensors show them. (dy [N, C, oh, ow] dtype, H, W, k, s, p) -> the message
+MAXPOOL_BWD_REFUSED = [
+    ((2, 2, BF), 4, 4, 3, 0, 1, "unsupported window"),        # s = 0 would divide by zero on the device
+    ((2, 2, BF), 4, 4, 16, 2, 1, "unsupported window"),       # k > 15 leaves the position byte
+    ((2, 2, BF), 4, 4, 0, 2, 0, "unsupported window"),
+    ((2, 2, BF), 4, 4, 3, 2, 2, "unsupported window"),        # 2p > k
+    ((2, 2, BF), 4, 4, 3, 2, -1, "unsupported window"),
+    ((2, 2, BF), 0, 4, 3, 2, 1, "H and W must be positive"),
+    ((2, 2, BF), 4, -4, 3, 2, 1, "H and W must be positive"),
+    ((2, 2, BF), 5, 4, 3, 2, 1, "is not the pooled size"),    # 5 rows pool to 3, floor and ceil
+    ((2, 2, BF), 4, 7, 3, 2, 1, "is not the pooled size"),    # 7 columns pool to 4
+    ((2, 4, BF), 4, 4, 3, 2, 1, "is not the pooled size"),    # 4 columns pool to 2 (floor) or 3 (ceil)
+    ((64, 64, BF), 1 << 16, 1 << 16, 1, 1024, 0, "too large for 32-bit indexing"),
+    ((2, 2, torch.float16), 4, 4, 3, 2, 1, "dy must be bf16 or fp32"),
+    ((2, 2, torch.float64), 4, 4, 3, 2, 1, "dy must be bf16 or fp32"),
+]
+
+
+@pytest.mark.parametrize("dy,h,w,k,s,p,msg", MAXPOOL_BWD_REFUSED)
+def test_maxpool_bwd_refuses_bad_geometry(dy, h, w, k, s, p, msg):
+    oh, ow, dt = dy
+    with pytest.raises(RuntimeError, match=f"maxpool_bwd: .*{msg}"):
+        _ext.require().maxpool_bwd(act(h=oh, w=ow, dtype=dt), pos(h=oh, w=ow), h, w, k, s, p)
+
+
+def test_maxpool_bwd_accepts_floor_and_ceil_sizes():
+    """[2, 2] is the floor-mode and [3, 3] the ceil-mode pooled size of a 6 x 6 image under 3x3/s2/p0: both pass the
+    geometry checks and reach the device check."""
+    for o in (2, 3):
+        with pytest.raises(RuntimeError, match="dy must be a GPU tensor"):
+            _ext.require().maxpool_bwd(act(h=o, w=o), pos(h=o, w=o), 6, 6, 3, 2, 0)
+
+
+def test_pool_fast_index_is_fdivs_domain():
+    """The multiply-shift index decode of the pool kernels only with work < 2^24 AND every divisor < 2^16."""
+    f = _ext.require().pool_fast_index
+    assert f((1 << 24) - 1, 3, 2365, 2364) and not f(1 << 24, 3, 2365, 2364)
+    assert f(100, 65535, 1, 1) and not f(100, 65536, 1, 1) and not f(100, 1, 65536, 1) and not f(100, 1, 1, 65536)
+    assert not f(2 * 1048577, 1, 1048577, 2)  # a [1, 8, 2, 1048577] image

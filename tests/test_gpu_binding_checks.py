@@ -201,3 +201,39 @@ def test_well_formed_calls_are_accepted(args):
         fn, a = _call(args, op)
         fn(*a)
     torch.cuda.synchronize()
+
+
+# ---- maxpool_bwd's geometry (the table of test_binding_checks.py, here with well-formed device tensors: refused
+# before any launch) ----
+MAXPOOL_BWD_REFUSED = [
+    ((2, 2, BF), 4, 4, 3, 0, 1, "unsupported window"),
+    ((2, 2, BF), 4, 4, 16, 2, 1, "unsupported window"),
+    ((2, 2, BF), 4, 4, 3, 2, 2, "unsupported window"),
+    ((2, 2, BF), 0, 4, 3, 2, 1, "H and W must be positive"),
+    ((2, 2, BF), 5, 4, 3, 2, 1, "is not the pooled size"),
+    ((2, 4, BF), 4, 4, 3, 2, 1, "is not the pooled size"),
+    ((64, 64, BF), 1 << 16, 1 << 16, 1, 1024, 0, "too large for 32-bit indexing"),
+    ((2, 2, torch.float16), 4, 4, 3, 2, 1, "dy must be bf16 or fp32"),
+]
+
+
+@pytest.mark.parametrize("dy,h,w,k,s,p,msg", MAXPOOL_BWD_REFUSED)
+def test_maxpool_bwd_refuses_bad_geometry(args, cuda, dy, h, w, k, s, p, msg):
+    oh, ow, dt = dy
+    d = torch.zeros(N, C, oh, ow, dtype=dt, device=cuda).contiguous(memory_format=torch.channels_last)
+    ps = torch.zeros(N, C, oh, ow, dtype=torch.uint8, device=cuda).contiguous(memory_format=torch.channels_last)
+    with pytest.raises(RuntimeError, match=f"maxpool_bwd: .*{msg}"):
+        args.C.maxpool_bwd(d, ps, h, w, k, s, p)
+    torch.cuda.synchronize()
+
+
+def test_fused_bn_pool_refuses_divisors_outside_the_fast_division(args, cuda):
+    """The fused BN+ReLU+max-pool kernels decode indices by multiply-shift only: a 65536-wide image is refused."""
+    x = torch.zeros(1, 8, 1, 65536, dtype=BF, device=cuda).contiguous(memory_format=torch.channels_last)
+    with pytest.raises(RuntimeError, match="bn_relu_maxpool: H, W and C / 8 must be below 65536"):
+        args.C.bn_relu_maxpool_fwd(x, None, None, None, None, 0.1, 1e-5, 3, 2, 1)
+    dyp = torch.zeros(1, 8, 1, 32768, dtype=BF, device=cuda).contiguous(memory_format=torch.channels_last)
+    ps = torch.zeros(1, 8, 1, 32768, dtype=torch.uint8, device=cuda).contiguous(memory_format=torch.channels_last)
+    with pytest.raises(RuntimeError, match="bn_relu_maxpool_bwd: .*below 65536"):
+        args.C.bn_relu_maxpool_bwd(dyp, ps, x, torch.zeros(56, device=cuda), None, 3, 2, 1)
+    torch.cuda.synchronize()

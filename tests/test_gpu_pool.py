@@ -67,7 +67,8 @@ def _pool_reference(x, k, s, p):
 @pytest.mark.parametrize("shape,p", [((2, 24, 10, 9), 1), ((3, 16, 7, 7), 0), ((2, 40, 15, 1), 1), ((1, 8, 29, 4), 1)])
 def test_maxpool3s1_ties_nan_inf_positions(cuda, dtype, shape, p):
     """The separable 3x3/s1 forward: values and 1-byte argmax positions equal the row-major
-    first-maximum scan, with ties, NaNs and -inf in the windows; strips of 7 rows with remainders."""
+    first-maximum scan, with ties, NaNs and -inf in the windows; the default strips of 4 rows, with remainders
+    (strips of 7 and the generic kernel: test_gpu_pool_exact.py, through set_pool3_sep)."""
     from distributed_learning_amd.ops import _ext
 
     torch.manual_seed(3)

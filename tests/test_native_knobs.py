@@ -53,6 +53,12 @@ STEPS = [
     ("halo_wgrad_off", "C.set_halo_wgrad(0) or C.halo_wgrad_eligible(64, 64, 56, 1)"),
     ("halo_wgrad_on", "C.set_halo_wgrad(1) or C.halo_wgrad_eligible(64, 64, 56, 1)"),
     ("halo_wgrad_cleared", "C.set_halo_wgrad(-1) or C.halo_wgrad_eligible(64, 64, 56, 1)"),
+    # POOL3_SEP: strip height of the 3x3/s1 max-pool forward (4 or 7; anything else: the generic kernel)
+    ("pool3", "C.pool3_strip_rows()"),
+    ("pool3_7", "C.set_pool3_sep(7) or C.pool3_strip_rows()"),
+    ("pool3_off", "C.set_pool3_sep(0) or C.pool3_strip_rows()"),
+    ("pool3_other", "C.set_pool3_sep(5) or C.pool3_strip_rows()"),
+    ("pool3_cleared", "C.set_pool3_sep(-1) or C.pool3_strip_rows()"),
     # APPLY_MAX_K (capped at 2048): K = 512, 1024, 2048, 4096
     ("apply", "[C.gemm_nt_apply_ok(4096, 64, k) for k in (512, 1024, 2048, 4096)]"),
     ("apply_set", "C.set_gemm_apply_max_k(256) or [C.gemm_nt_apply_ok(4096, 64, k) for k in (256, 512)]"),
@@ -93,6 +99,7 @@ DEFAULTS = {
     "red": 1024, "red_set": 64, "red_cleared": 1024,
     "halo": [True, True],
     "halo_wgrad": True, "halo_wgrad_off": False, "halo_wgrad_on": True, "halo_wgrad_cleared": True,
+    "pool3": 4, "pool3_7": 7, "pool3_off": 0, "pool3_other": 0, "pool3_cleared": 4,
     "apply": [True, False, False, False], "apply_set": [True, False], "apply_set_cap": [True, False],
     "apply_cleared": [True, False, False, False],
     "stream": [128, 0, 64, True], "stream_off": [0, 0, False], "stream_forced": [128, 64, True],
@@ -105,8 +112,9 @@ CASES = {
     "non_default": (
         {"DLA_TILE512": "0", "DLA_TILE256_MIN_K_STATS": "512", "DLA_TN256": "0", "DLA_SPLITK_BLOCKS": "256",
          "DLA_BN_RED_BLOCKS": "300", "DLA_HALO": "1", "DLA_HALO_WGRAD": "0", "DLA_APPLY_MAX_K": "1024",
-         "DLA_GEMM_STREAM": "0"},
+         "DLA_GEMM_STREAM": "0", "DLA_POOL3_SEP": "7"},
         {"conv_tile": T128,
+         "pool3": 7, "pool3_cleared": 7,
          "tile_stats": T128, "tile_stats_cleared": T128,  # changed: the setter's -1 used to give T256 (min K 256)
          "tn": 16, "tn_off": 16, "tn_on": 32, "tn_cleared": 16,  # half of the defaults': SPLITK_BLOCKS=256
          "splitk": [256, 64], "splitk_cleared": [256, 64],
@@ -126,8 +134,9 @@ CASES = {
         # HALO off; GEMM_STREAM on by the environment is not "forced on"; APPLY_MAX_K above its cap; switches
         # parse the first character only
         {"DLA_HALO": "0", "DLA_GEMM_STREAM": "1", "DLA_APPLY_MAX_K": "4096", "DLA_TN256": "off",
-         "DLA_HALO_WGRAD": "00", "DLA_SPLITK_BLOCKS": "-3", "DLA_BN_RED_BLOCKS": "abc"},
+         "DLA_HALO_WGRAD": "00", "DLA_SPLITK_BLOCKS": "-3", "DLA_BN_RED_BLOCKS": "abc", "DLA_POOL3_SEP": "0"},
         {"halo": [False, False],
+         "pool3": 0, "pool3_cleared": 0,
          "halo_wgrad": False, "halo_wgrad_cleared": False,
          "apply": [True, True, True, False], "apply_cleared": [True, True, True, False]},
     ),
