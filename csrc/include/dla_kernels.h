@@ -161,6 +161,14 @@ void launch_randint_fill(int64_t* out, int64_t n, int64_t high, uint64_t seed, u
 void launch_augment(const uint8_t* src, void* out, int dtype, const float* geom, const uint8_t* flip,
                     const float* scale, const float* bias, int N, int Hs, int Ws, int Ho, int Wo, int pad,
                     hipStream_t stream);
+// Mixup / CutMix in the same pass: partner[n] in [0, N), lam[n] in [0, 1], box[n] = (y0, x0, y1, x1) on the
+// output grid (16-byte aligned). With A(j) the plain result for source image j with geom[j] and flip[j]:
+// w = inside box[n] ? 0 : lam[n]; out = fmaf(w, A(n), (1 - w) * A(partner[n])). blend = false is the select form
+// (one sample per pixel, from n or its partner), valid only when every lam is 1; blend = true samples both.
+void launch_augment_mix(const uint8_t* src, void* out, int dtype, const float* geom, const uint8_t* flip,
+                        const int32_t* partner, const float* lam, const int32_t* box, const float* scale,
+                        const float* bias, int N, int Hs, int Ws, int Ho, int Wo, int pad, bool blend,
+                        hipStream_t stream);
 
 // ---- fused log-softmax + NLL (loss.hip) -----------------------------------------------------
 // logits [B, C] (dtype), target [B] int64 (< 0 = ignored). ws: 3*B floats (row lse, row loss,
@@ -183,6 +191,18 @@ void launch_xent_metrics_fwd(const void* logits, const int64_t* target, float* w
 void launch_xent_smooth_bwd(const void* logits, const int64_t* target, const float* ws, const float* stats,
                             const float* gout, void* dlogits, int B, int C, float eps, int dtype,
                             hipStream_t stream);
+
+// Pair-target variant (Mixup / CutMix): row targets (ta, tb) weighted (lam[row], 1 - lam[row]); a row is valid iff
+// both targets are in [0, C). ws: 3*B + 1 floats (row lse, row loss, row valid, then the mean loss stats[0] /
+// stats[1], NaN without a valid row). stats[2] = {sum of row losses over valid rows, valid rows}, summed by one
+// workgroup in a fixed order. Row loss = lse - (1-eps)*(lam*x_ta + (1-lam)*x_tb) - (eps/C)*sum_c x_c, a term of
+// weight exactly 0 left out. Backward: dlogits = (softmax - (1-eps)*(lam*onehot_ta + (1-lam)*onehot_tb) - eps/C) *
+// gout / stats[1], zeros for ignored rows. B == 0 is allowed.
+void launch_xent_mix_fwd(const void* logits, const int64_t* target_a, const int64_t* target_b, const float* lam,
+                         float* ws, float* stats, int B, int C, float eps, int dtype, hipStream_t stream);
+void launch_xent_mix_bwd(const void* logits, const int64_t* target_a, const int64_t* target_b, const float* lam,
+                         const float* ws, const float* stats, const float* gout, void* dlogits, int B, int C,
+                         float eps, int dtype, hipStream_t stream);
 
 // ---- fused BatchNorm + residual + ReLU, NHWC (bn_act.hip) ------------------------------------
 // x/res/y/dy/dx/dres: [M, C] row-major (channels_last activations), C % 8 == 0, 16-byte aligned.

@@ -309,6 +309,168 @@ __global__ __launch_bounds__(kXWaves * 64) void xent_smooth_bwd_kernel(const T* 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pair-target (Mixup / CutMix) label-smoothed cross-entropy: row targets (ta, tb) with weights
+// (lam, 1 - lam). The same row kernels as above without the rank: both target logits are read first
+// (two wave-uniform loads), then every logit is loaded once in forward and once in backward.
+//   xt  = lam * x[ta] + (1 - lam) * x[tb]      (a term whose weight is exactly 0 is left out)
+//   row = lse - (1 - eps) * xt - (eps > 0 ? eps * mean(x) : 0)
+// A row is valid iff both targets are in [0, C). With lam == 1 (or 0) every operation on the row is
+// the one xent_metric_rows_kernel / xent_smooth_bwd_kernel does for ta (tb), in the same order.
+// ------------------------------------------------------------------------------------------------
+struct MixRowAcc {
+  OnlineLse o;
+  float sum = 0.f;  // plain sum of the logits, for the smoothing term
+};
+
+template <typename T, bool kVec>
+__global__ __launch_bounds__(kXWaves * 64) void xent_mix_rows_kernel(const T* __restrict__ logits,
+                                                                     const int64_t* __restrict__ target_a,
+                                                                     const int64_t* __restrict__ target_b,
+                                                                     const float* __restrict__ lam,
+                                                                     float* __restrict__ ws, int B, int C, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kXWaves + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const T* x = logits + (int64_t)row * C;
+  const int64_t a64 = target_a[row], b64 = target_b[row];
+  const bool valid = a64 >= 0 && a64 < C && b64 >= 0 && b64 < C;
+  const float xa = Cvt<T>::to_f32(x[valid ? (int)a64 : 0]);  // C >= 1: column 0 exists also for an ignored row
+  const float xb = Cvt<T>::to_f32(x[valid ? (int)b64 : 0]);
+  MixRowAcc a;
+  if constexpr (kVec) {
+    constexpr int N = Raw16<T>::kN;
+    const int nvec = C / N;  // exact: the pitch is a multiple of 16 bytes
+    for (int v0 = lane; v0 < nvec; v0 += 64 * kXUnroll) {
+      Raw16<T> r[kXUnroll];
+#pragma unroll
+      for (int u = 0; u < kXUnroll; ++u)
+        if (v0 + 64 * u < nvec) r[u].load(x + (int64_t)(v0 + 64 * u) * N);
+#pragma unroll
+      for (int u = 0; u < kXUnroll; ++u) {
+        if (v0 + 64 * u >= nvec) break;
+        float f[N];
+        float vm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          f[j] = r[u].get(j);
+          vm = fmaxf(vm, f[j]);
+        }
+        a.o.rescale(fmaxf(a.o.m, vm));
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          a.o.add(f[j]);
+          a.sum += f[j];
+        }
+      }
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) {
+      const float f = Cvt<T>::to_f32(x[c]);
+      a.o.rescale(fmaxf(a.o.m, f));
+      a.o.add(f);
+      a.sum += f;
+    }
+  }
+  const float m = wave_max(a.o.m);
+  a.o.rescale(m);  // a lane still at -inf keeps its s (0, or NaN from a NaN logit)
+  const float s = wave_sum(a.o.s);
+  const float sum = wave_sum(a.sum);
+  if (lane == 0) {
+    const float lse = m + __logf(s);
+    const float wa = lam[row], wb = 1.f - wa;
+    // a weight of exactly 0 drops its term, so a -inf logit at that class does not turn 0 * inf into NaN
+    const float xt = (wa != 0.f ? wa * xa : 0.f) + (wb != 0.f ? wb * xb : 0.f);
+    const float smooth = eps > 0.f ? eps * (sum / (float)C) : 0.f;
+    ws[row] = lse;
+    ws[B + row] = valid ? lse - (1.f - eps) * xt - smooth : 0.f;
+    ws[2 * B + row] = valid ? 1.f : 0.f;
+  }
+}
+
+// stats = [sum of row losses over valid rows, valid rows]; ws[3 * B] = stats[0] / stats[1], the mean loss (NaN
+// without a valid row). One workgroup, the order of xent_stats_kernel, no float atomics.
+__global__ __launch_bounds__(256) void xent_mix_mean_kernel(float* __restrict__ ws, float* __restrict__ stats, int B) {
+  __shared__ float red[2][4];
+  float acc[2] = {0.f, 0.f};
+  for (int i = threadIdx.x; i < B; i += 256) {
+    acc[0] += ws[B + i];
+    acc[1] += ws[2 * B + i];
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    acc[q] = wave_sum(acc[q]);
+    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      tot[q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
+      stats[q] = tot[q];
+    }
+    ws[3 * B] = tot[1] > 0.f ? tot[0] / tot[1] : NAN;
+  }
+}
+
+template <typename T, bool kVec>
+__global__ __launch_bounds__(kXWaves * 64) void xent_mix_bwd_kernel(const T* __restrict__ logits,
+                                                                    const int64_t* __restrict__ target_a,
+                                                                    const int64_t* __restrict__ target_b,
+                                                                    const float* __restrict__ lam,
+                                                                    const float* __restrict__ ws,
+                                                                    const float* __restrict__ stats,
+                                                                    const float* __restrict__ gout,
+                                                                    T* __restrict__ dlogits, int B, int C, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kXWaves + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const T* x = logits + (int64_t)row * C;
+  T* d = dlogits + (int64_t)row * C;
+  const int64_t a64 = target_a[row], b64 = target_b[row];
+  const bool valid = a64 >= 0 && a64 < C && b64 >= 0 && b64 < C;
+  const int ta = valid ? (int)a64 : -1, tb = valid ? (int)b64 : -1;
+  const float lse = ws[row];
+  const float g = valid ? gout[0] / stats[1] : 0.f;  // one division per row
+  const float wa = lam[row];
+  const float hot = 1.f - eps, uni = eps / (float)C;
+  const float ha = hot * wa, hb = hot * (1.f - wa);  // ta == tb: the two terms add
+  if constexpr (kVec) {
+    constexpr int N = Raw16<T>::kN;
+    const int nvec = C / N;
+    for (int v0 = lane; v0 < nvec; v0 += 64 * kXUnroll) {
+      Raw16<T> r[kXUnroll];
+      if (valid) {
+#pragma unroll
+        for (int u = 0; u < kXUnroll; ++u)
+          if (v0 + 64 * u < nvec) r[u].load(x + (int64_t)(v0 + 64 * u) * N);
+      }
+#pragma unroll
+      for (int u = 0; u < kXUnroll; ++u) {
+        if (v0 + 64 * u >= nvec) break;
+        const int c0 = (v0 + 64 * u) * N;
+        Raw16<T> o;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const float h = (c0 + j == ta ? ha : 0.f) + (c0 + j == tb ? hb : 0.f);
+          o.set(j, valid ? (__expf(r[u].get(j) - lse) - h - uni) * g : 0.f);
+        }
+        o.store(d + c0);
+      }
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) {
+      float v = 0.f;
+      if (valid) {
+        const float h = (c == ta ? ha : 0.f) + (c == tb ? hb : 0.f);
+        v = (__expf(Cvt<T>::to_f32(x[c]) - lse) - h - uni) * g;
+      }
+      d[c] = Cvt<T>::from_f32(v);
+    }
+  }
+}
+
 static bool xent_rows_vectorisable(const void* p, int C, int dtype) {
   const size_t pitch = (size_t)C * (dtype == kF32 ? 4 : 2);
   return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (pitch % 16 == 0);
@@ -346,6 +508,41 @@ void launch_xent_smooth_bwd(const void* logits, const int64_t* target, const flo
     if (vec) DLA_XENT_BWD(bf16_t, true); else DLA_XENT_BWD(bf16_t, false);
   }
 #undef DLA_XENT_BWD
+}
+
+void launch_xent_mix_fwd(const void* logits, const int64_t* target_a, const int64_t* target_b, const float* lam,
+                         float* ws, float* stats, int B, int C, float eps, int dtype, hipStream_t stream) {
+  if (B > 0) {
+    dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
+    const bool vec = xent_rows_vectorisable(logits, C, dtype);
+#define DLA_XENT_MIX_ROWS(T, V)                                                                                   \
+  hipLaunchKernelGGL((xent_mix_rows_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target_a, target_b, \
+                     lam, ws, B, C, eps)
+    if (dtype == kF32) {
+      if (vec) DLA_XENT_MIX_ROWS(float, true); else DLA_XENT_MIX_ROWS(float, false);
+    } else {
+      if (vec) DLA_XENT_MIX_ROWS(bf16_t, true); else DLA_XENT_MIX_ROWS(bf16_t, false);
+    }
+#undef DLA_XENT_MIX_ROWS
+  }
+  hipLaunchKernelGGL(xent_mix_mean_kernel, dim3(1), dim3(256), 0, stream, ws, stats, B);
+}
+
+void launch_xent_mix_bwd(const void* logits, const int64_t* target_a, const int64_t* target_b, const float* lam,
+                         const float* ws, const float* stats, const float* gout, void* dlogits, int B, int C,
+                         float eps, int dtype, hipStream_t stream) {
+  if (B <= 0) return;
+  dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
+  const bool vec = xent_rows_vectorisable(logits, C, dtype) && xent_rows_vectorisable(dlogits, C, dtype);
+#define DLA_XENT_MIX_BWD(T, V)                                                                                   \
+  hipLaunchKernelGGL((xent_mix_bwd_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target_a, target_b, \
+                     lam, ws, stats, gout, (T*)dlogits, B, C, eps)
+  if (dtype == kF32) {
+    if (vec) DLA_XENT_MIX_BWD(float, true); else DLA_XENT_MIX_BWD(float, false);
+  } else {
+    if (vec) DLA_XENT_MIX_BWD(bf16_t, true); else DLA_XENT_MIX_BWD(bf16_t, false);
+  }
+#undef DLA_XENT_MIX_BWD
 }
 
 }  // namespace dla

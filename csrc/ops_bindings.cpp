@@ -427,42 +427,77 @@ void randint_(at::Tensor t, int64_t high, int64_t seed, int64_t offset, c10::opt
 
 // out: logical [N, 3, Ho, Wo] in channels-last memory (dense [N, Ho, Wo, 3]), possibly a slice of a larger
 // buffer. Everything is checked before the launch; the kernel indexes elements with 32 bits.
-void augment_(at::Tensor src, at::Tensor out, at::Tensor geom, at::Tensor flip, at::Tensor scale, at::Tensor bias,
-              int64_t pad) {
+struct AugmentDims {
+  int N, Hs, Ws, Ho, Wo, dtype;
+};
+
+// The checks augment_ and augment_mix_ share; `op` prefixes the messages.
+static AugmentDims check_augment_args(const char* op, const at::Tensor& src, const at::Tensor& out,
+                                      const at::Tensor& geom, const at::Tensor& flip, const at::Tensor& scale,
+                                      const at::Tensor& bias, int64_t pad) {
   TORCH_CHECK(src.is_cuda() && out.is_cuda() && geom.is_cuda() && flip.is_cuda() && scale.is_cuda() && bias.is_cuda(),
-              "augment_: every tensor must be on the GPU");
+              op, ": every tensor must be on the GPU");
   for (const at::Tensor* t : {&out, &geom, &flip, &scale, &bias})
-    TORCH_CHECK(t->device() == src.device(), "augment_: tensors are on different devices");
-  TORCH_CHECK(src.scalar_type() == at::kByte, "augment_: src must be uint8, got ", src.scalar_type());
-  TORCH_CHECK(src.dim() == 4 && src.size(3) == 3, "augment_: src must be [N, Hs, Ws, 3] (3 channels last)");
-  TORCH_CHECK(src.is_contiguous(), "augment_: src must be contiguous");
+    TORCH_CHECK(t->device() == src.device(), op, ": tensors are on different devices");
+  TORCH_CHECK(src.scalar_type() == at::kByte, op, ": src must be uint8, got ", src.scalar_type());
+  TORCH_CHECK(src.dim() == 4 && src.size(3) == 3, op, ": src must be [N, Hs, Ws, 3] (3 channels last)");
+  TORCH_CHECK(src.is_contiguous(), op, ": src must be contiguous");
   const int out_dtype = dtype_code(out);
-  TORCH_CHECK(out.dim() == 4 && out.size(1) == 3 && out.size(0) == src.size(0),
-              "augment_: out must be [N, 3, Ho, Wo] with src's N");
+  TORCH_CHECK(out.dim() == 4 && out.size(1) == 3 && out.size(0) == src.size(0), op,
+              ": out must be [N, 3, Ho, Wo] with src's N");
   const int64_t N = src.size(0), Hs = src.size(1), Ws = src.size(2), Ho = out.size(2), Wo = out.size(3);
-  TORCH_CHECK(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "augment_: empty image");
+  TORCH_CHECK(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, op, ": empty image");
   const int64_t want[4] = {Ho * Wo * 3, 1, Wo * 3, 3};
   for (int d = 0; d < 4; ++d)
-    TORCH_CHECK(out.size(d) == 1 || out.stride(d) == want[d],
-                "augment_: out must be channels-last memory (dense [N, Ho, Wo, 3]); stride ", out.stride(d), " of dim ",
-                d, ", expected ", want[d]);
+    TORCH_CHECK(out.size(d) == 1 || out.stride(d) == want[d], op,
+                ": out must be channels-last memory (dense [N, Ho, Wo, 3]); stride ", out.stride(d), " of dim ", d,
+                ", expected ", want[d]);
   TORCH_CHECK(geom.scalar_type() == at::kFloat && geom.dim() == 2 && geom.size(0) == N && geom.size(1) == 4 &&
                   geom.is_contiguous(),
-              "augment_: geom must be a contiguous fp32 [N, 4]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(geom.data_ptr()) % 16 == 0, "augment_: geom must be 16-byte aligned");
+              op, ": geom must be a contiguous fp32 [N, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(geom.data_ptr()) % 16 == 0, op, ": geom must be 16-byte aligned");
   // a row's two x taps are read by one 8-byte load that is kept inside the tensor
-  TORCH_CHECK(N == 0 || src.numel() >= 9, "augment_: src must hold at least three pixels");
-  TORCH_CHECK(flip.scalar_type() == at::kByte && flip.dim() == 1 && flip.size(0) == N && flip.is_contiguous(),
-              "augment_: flip must be a contiguous uint8 [N]");
+  TORCH_CHECK(N == 0 || src.numel() >= 9, op, ": src must hold at least three pixels");
+  TORCH_CHECK(flip.scalar_type() == at::kByte && flip.dim() == 1 && flip.size(0) == N && flip.is_contiguous(), op,
+              ": flip must be a contiguous uint8 [N]");
   for (const at::Tensor* t : {&scale, &bias})
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 3 && t->is_contiguous(),
-                "augment_: scale and bias must be contiguous fp32 [3]");
-  TORCH_CHECK(pad >= 0 && pad < (1 << 20), "augment_: pad must be >= 0, got ", pad);
-  TORCH_CHECK(src.numel() < (int64_t(1) << 31) && out.numel() < (int64_t(1) << 31),
-              "augment_: src and out must have fewer than 2^31 elements");
-  launch_augment(src.data_ptr<uint8_t>(), out.data_ptr(), out_dtype, geom.data_ptr<float>(), flip.data_ptr<uint8_t>(),
-                 scale.data_ptr<float>(), bias.data_ptr<float>(), (int)N, (int)Hs, (int)Ws, (int)Ho, (int)Wo, (int)pad,
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 3 && t->is_contiguous(), op,
+                ": scale and bias must be contiguous fp32 [3]");
+  TORCH_CHECK(pad >= 0 && pad < (1 << 20), op, ": pad must be >= 0, got ", pad);
+  TORCH_CHECK(src.numel() < (int64_t(1) << 31) && out.numel() < (int64_t(1) << 31), op,
+              ": src and out must have fewer than 2^31 elements");
+  return AugmentDims{(int)N, (int)Hs, (int)Ws, (int)Ho, (int)Wo, out_dtype};
+}
+
+void augment_(at::Tensor src, at::Tensor out, at::Tensor geom, at::Tensor flip, at::Tensor scale, at::Tensor bias,
+              int64_t pad) {
+  const AugmentDims d = check_augment_args("augment_", src, out, geom, flip, scale, bias, pad);
+  launch_augment(src.data_ptr<uint8_t>(), out.data_ptr(), d.dtype, geom.data_ptr<float>(), flip.data_ptr<uint8_t>(),
+                 scale.data_ptr<float>(), bias.data_ptr<float>(), d.N, d.Hs, d.Ws, d.Ho, d.Wo, (int)pad,
                  current_stream(out));
+}
+
+// augment_ with Mixup / CutMix: per sample a partner image, a weight and a box on the output grid (dla_kernels.h).
+// The values of partner, lam and box live on the device and are the caller's to keep in range (ops/augment.py
+// checks host tensors); blend = false promises lam == 1 everywhere.
+void augment_mix_(at::Tensor src, at::Tensor out, at::Tensor geom, at::Tensor flip, at::Tensor partner, at::Tensor lam,
+                  at::Tensor box, at::Tensor scale, at::Tensor bias, int64_t pad, bool blend) {
+  const AugmentDims d = check_augment_args("augment_mix_", src, out, geom, flip, scale, bias, pad);
+  for (const at::Tensor* t : {&partner, &lam, &box})
+    TORCH_CHECK(t->is_cuda() && t->device() == src.device(), "augment_mix_: partner, lam and box must be on src's GPU");
+  TORCH_CHECK(partner.scalar_type() == at::kInt && partner.dim() == 1 && partner.size(0) == d.N &&
+                  partner.is_contiguous(),
+              "augment_mix_: partner must be a contiguous int32 [N]");
+  TORCH_CHECK(lam.scalar_type() == at::kFloat && lam.dim() == 1 && lam.size(0) == d.N && lam.is_contiguous(),
+              "augment_mix_: lam must be a contiguous fp32 [N]");
+  TORCH_CHECK(box.scalar_type() == at::kInt && box.dim() == 2 && box.size(0) == d.N && box.size(1) == 4 &&
+                  box.is_contiguous(),
+              "augment_mix_: box must be a contiguous int32 [N, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(box.data_ptr()) % 16 == 0, "augment_mix_: box must be 16-byte aligned");
+  launch_augment_mix(src.data_ptr<uint8_t>(), out.data_ptr(), d.dtype, geom.data_ptr<float>(),
+                     flip.data_ptr<uint8_t>(), partner.data_ptr<int32_t>(), lam.data_ptr<float>(),
+                     box.data_ptr<int32_t>(), scale.data_ptr<float>(), bias.data_ptr<float>(), d.N, d.Hs, d.Ws, d.Ho,
+                     d.Wo, (int)pad, blend, current_stream(out));
 }
 
 std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor target) {
@@ -533,6 +568,46 @@ at::Tensor xent_smooth_bwd(at::Tensor logits, at::Tensor target, at::Tensor ws, 
   return d;
 }
 
+static void check_xent_mix_args(const at::Tensor& logits, const at::Tensor& target_a, const at::Tensor& target_b,
+                                const at::Tensor& lam, double eps, const char* op) {
+  check_xent_args(logits, target_a, eps, op);
+  check_xent_args(logits, target_b, eps, op);
+  check_dev(lam, "lam");
+  TORCH_CHECK(lam.scalar_type() == at::kFloat && lam.numel() == logits.size(0) && lam.is_contiguous(), op,
+              ": lam must be a contiguous fp32 [B]");
+  TORCH_CHECK(lam.device() == logits.device(), op, ": logits and lam are on different devices");
+}
+
+std::vector<at::Tensor> xent_mix_fwd(at::Tensor logits, at::Tensor target_a, at::Tensor target_b, at::Tensor lam,
+                                     double eps) {
+  check_xent_mix_args(logits, target_a, target_b, lam, eps, "xent_mix_fwd");
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto ws = at::empty({3 * (int64_t)B + 1}, f32);
+  auto stats = at::empty({2}, f32);
+  launch_xent_mix_fwd(logits.data_ptr(), target_a.data_ptr<int64_t>(), target_b.data_ptr<int64_t>(),
+                      lam.data_ptr<float>(), ws.data_ptr<float>(), stats.data_ptr<float>(), B, C, (float)eps,
+                      dtype_code(logits), current_stream(logits));
+  return {stats, ws};
+}
+
+at::Tensor xent_mix_bwd(at::Tensor logits, at::Tensor target_a, at::Tensor target_b, at::Tensor lam, at::Tensor ws,
+                        at::Tensor stats, at::Tensor gout, double eps) {
+  check_xent_mix_args(logits, target_a, target_b, lam, eps, "xent_mix_bwd");
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  check_dev(ws, "ws");
+  check_dev(stats, "stats");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 3 * (int64_t)B + 1, "xent_mix_bwd: bad workspace");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == 2, "xent_mix_bwd: bad stats");
+  TORCH_CHECK(gout.is_cuda() && gout.numel() == 1, "xent_mix_bwd: gout must be one value on the GPU");
+  auto d = at::empty_like(logits);
+  auto g = gout.to(at::kFloat).contiguous();
+  launch_xent_mix_bwd(logits.data_ptr(), target_a.data_ptr<int64_t>(), target_b.data_ptr<int64_t>(),
+                      lam.data_ptr<float>(), ws.data_ptr<float>(), stats.data_ptr<float>(), g.data_ptr<float>(),
+                      d.data_ptr(), B, C, (float)eps, dtype_code(logits), current_stream(logits));
+  return d;
+}
+
 void bind_ops(pybind11::module& m) {
   pybind11::class_<SgdTable>(m, "SgdTable")
       .def(pybind11::init<std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>,
@@ -569,12 +644,22 @@ void bind_ops(pybind11::module& m) {
         "uint8 [N,Hs,Ws,3] -> channels-last [N,3,Ho,Wo]: per-sample crop, bilinear resample, flip, normalise, cast",
         pybind11::arg("src"), pybind11::arg("out"), pybind11::arg("geom"), pybind11::arg("flip"),
         pybind11::arg("scale"), pybind11::arg("bias"), pybind11::arg("pad") = 0);
+  m.def("augment_mix_", &augment_mix_,
+        "augment_ with Mixup / CutMix: out = fmaf(w, A(n), (1 - w) * A(partner[n])), w = 0 inside box[n] else lam[n]; "
+        "blend = false samples once per pixel and needs lam == 1",
+        pybind11::arg("src"), pybind11::arg("out"), pybind11::arg("geom"), pybind11::arg("flip"),
+        pybind11::arg("partner"), pybind11::arg("lam"), pybind11::arg("box"), pybind11::arg("scale"),
+        pybind11::arg("bias"), pybind11::arg("pad") = 0, pybind11::arg("blend") = true);
   m.def("xent_fwd", &xent_fwd, "fused log-softmax + NLL forward");
   m.def("xent_bwd", &xent_bwd, "fused log-softmax + NLL backward");
   m.def("xent_metrics_fwd", &xent_metrics_fwd,
         "label-smoothed cross-entropy forward: (stats[4] = loss sum, valid rows, top-1 correct, top-k correct; ws, whose "
         "last element is the mean loss)");
   m.def("xent_smooth_bwd", &xent_smooth_bwd, "label-smoothed cross-entropy backward");
+  m.def("xent_mix_fwd", &xent_mix_fwd,
+        "pair-target label-smoothed cross-entropy forward: (stats[2] = loss sum, valid rows; ws, whose last element is "
+        "the mean loss)");
+  m.def("xent_mix_bwd", &xent_mix_bwd, "pair-target label-smoothed cross-entropy backward");
 }
 
 }  // namespace dla

@@ -75,6 +75,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "(CIFAR models), centre crop for evaluation")
     p.add_argument("--aug_scale_min", type=float, default=0.08,
                    help="smallest area fraction of the random-resized crop, in (0, 1]")
+    p.add_argument("--mixup_alpha", type=float, default=0.0,
+                   help="Mixup: blend every sample with a partner, weight ~ Beta(alpha, alpha) per batch (0 = off; "
+                        "needs --augment standard, whose kernel does the mixing)")
+    p.add_argument("--cutmix_alpha", type=float, default=0.0,
+                   help="CutMix: paste a box of the partner, area fraction 1 - Beta(alpha, alpha) per batch (0 = off; "
+                        "needs --augment standard)")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5,
+                   help="with both alphas set: the probability that a batch uses CutMix, in [0, 1]")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--master_port", type=int, default=29501)
     # MI355X options
@@ -125,6 +133,12 @@ def parse_args(argv: Optional[List[str]] = None):
         parser.error("--topk must be >= 1")
     if not 0.0 < config.aug_scale_min <= 1.0:
         parser.error("--aug_scale_min must be in (0, 1]")
+    if not (config.mixup_alpha >= 0 and config.cutmix_alpha >= 0):
+        parser.error("--mixup_alpha and --cutmix_alpha must be >= 0")
+    if not 0.0 <= config.mix_switch_prob <= 1.0:
+        parser.error("--mix_switch_prob must be in [0, 1]")
+    if (config.mixup_alpha > 0 or config.cutmix_alpha > 0) and config.augment == "none":
+        parser.error("--mixup_alpha / --cutmix_alpha need --augment standard: the mixing lives in that kernel")
     if config.augment != "none":
         from .models import MODELS
 

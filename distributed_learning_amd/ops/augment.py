@@ -21,6 +21,10 @@ With step 1 and integer offsets ``fy = fx = 0``: the blend is one source byte an
 
 The crop boxes and flips of a batch come from :class:`AugmentParams`, a pure function of
 ``(seed, stream, step)`` computed on the host.
+
+:func:`augment_mix` is the same pass with Mixup / CutMix: every sample is combined with a partner image that is
+sampled with its own geometry (mixed instantiations of the same kernel); :class:`MixParams` draws its per-batch
+parameters, again as a pure function of ``(seed, stream, step)``.
 """
 from __future__ import annotations
 
@@ -107,6 +111,60 @@ def augment(src_u8: torch.Tensor, geom: torch.Tensor, flip: torch.Tensor, mean: 
     return out
 
 
+def _check_mix(n: int, partner, lam, box, out_hw, blend: bool) -> None:
+    """Shapes and dtypes always; the values of tensors that live on the host (a device tensor is not read back)."""
+    if tuple(partner.shape) != (n,) or partner.dtype != torch.int32:
+        raise ValueError(f"augment_mix: partner must be int32 [{n}], got {partner.dtype} {tuple(partner.shape)}")
+    if tuple(lam.shape) != (n,) or lam.dtype != torch.float32:
+        raise ValueError(f"augment_mix: lam must be fp32 [{n}], got {lam.dtype} {tuple(lam.shape)}")
+    if tuple(box.shape) != (n, 4) or box.dtype != torch.int32:
+        raise ValueError(f"augment_mix: box must be int32 [{n}, 4], got {box.dtype} {tuple(box.shape)}")
+    if n == 0:
+        return
+    ho, wo = out_hw
+    if partner.device.type == "cpu" and not bool(((partner >= 0) & (partner < n)).all()):
+        raise ValueError(f"augment_mix: partner must be in [0, {n})")
+    if lam.device.type == "cpu":
+        if not bool(((lam >= 0) & (lam <= 1)).all()):  # NaN fails too
+            raise ValueError("augment_mix: lam must be in [0, 1]")
+        if not blend and not bool((lam == 1).all()):
+            raise ValueError("augment_mix: blend=False samples one image per pixel and needs lam == 1 everywhere")
+    if box.device.type == "cpu":
+        y0, x0, y1, x1 = box.unbind(1)
+        if not bool(((0 <= y0) & (y0 <= y1) & (y1 <= ho) & (0 <= x0) & (x0 <= x1) & (x1 <= wo)).all()):
+            raise ValueError(f"augment_mix: boxes must satisfy 0 <= y0 <= y1 <= {ho} and 0 <= x0 <= x1 <= {wo}")
+
+
+def augment_mix(src_u8: torch.Tensor, geom: torch.Tensor, flip: torch.Tensor, partner: torch.Tensor,
+                lam: torch.Tensor, box: torch.Tensor, mean: Sequence[float], std: Sequence[float],
+                out_hw: Tuple[int, int], dtype: torch.dtype, pad: int = 0, blend: bool = True) -> torch.Tensor:
+    """:func:`augment` with Mixup / CutMix in the same pass. With ``A(j)`` the fp32 value :func:`augment` gives
+    for source image ``j`` with ``geom[j]`` and ``flip[j]``, ``p = partner[n]`` and ``box[n] = (y0, x0, y1, x1)``
+    on the output grid (independent of either image's flip)::
+
+        w   = 0 if y0 <= oy < y1 and x0 <= ox < x1 else lam[n]
+        out = fmaf(w, A(n)[oy, ox, c], (1 - w) * A(p)[oy, ox, c])       (fp32, then one cast)
+
+    Mixup is an empty box with ``0 < lam < 1``, CutMix ``lam = 1`` with a box. ``partner`` int32 ``[N]``, ``lam``
+    fp32 ``[N]`` and ``box`` int32 ``[N, 4]`` may live on the host (:meth:`MixParams.params`), where their values
+    are range-checked; a device tensor's values are the caller's to keep in range. ``blend=False`` is the select
+    form -- one sample per pixel, from ``n`` or ``p`` -- and needs ``lam == 1`` for every sample."""
+    out_hw = (int(out_hw[0]), int(out_hw[1]))
+    _check(src_u8, geom, flip, out_hw, dtype, pad)
+    n = src_u8.shape[0]
+    _check_mix(n, partner, lam, box, out_hw, bool(blend))
+    dev = src_u8.device
+    geom, flip = geom.to(dev, non_blocking=True).contiguous(), flip.to(dev, non_blocking=True).contiguous()
+    partner, lam, box = (t.to(dev, non_blocking=True).contiguous() for t in (partner, lam, box))
+    scale, bias = _coefficients(mean, std, dev)
+    if dev.type != "cuda":
+        return _augment_mix_torch(src_u8, geom, flip, partner, lam, box, scale, bias, out_hw, dtype, int(pad))
+    C = _ext.require()
+    out = torch.empty((n, out_hw[0], out_hw[1], 3), device=dev, dtype=dtype).permute(0, 3, 1, 2)
+    C.augment_mix_(src_u8, out, geom, flip, partner, lam, box, scale, bias, int(pad), bool(blend))
+    return out
+
+
 def _taps(s: torch.Tensor, size: int, pad: int):
     """Both taps of one axis from the fp32 sample coordinates ``s`` [N, L]: (index0, index1, inside0, inside1,
     fraction); an index is only meaningful where its ``inside`` is set."""
@@ -123,6 +181,28 @@ def _taps(s: torch.Tensor, size: int, pad: int):
 
 
 def _augment_torch(src, geom, flip, scale, bias, out_hw, dtype, pad) -> torch.Tensor:
+    return _augment_values(src, geom, flip, scale, bias, out_hw, pad).to(dtype).permute(0, 3, 1, 2)
+
+
+def _augment_mix_torch(src, geom, flip, partner, lam, box, scale, bias, out_hw, dtype, pad) -> torch.Tensor:
+    """The mixed definition on the CPU: both images sampled, then ``fmaf(w, a, (1 - w) * b)`` with the fp32
+    product ``(1 - w) * b`` and the exact product ``w * a`` summed in float64."""
+    ho, wo = out_hw
+    p = partner.long()
+    a = _augment_values(src, geom, flip, scale, bias, out_hw, pad)
+    b = _augment_values(src[p], geom[p], flip[p], scale, bias, out_hw, pad)
+    oy = torch.arange(ho, device=src.device)[None, :, None]
+    ox = torch.arange(wo, device=src.device)[None, None, :]
+    y0, x0, y1, x1 = (box[:, i].long()[:, None, None] for i in range(4))
+    inbox = (oy >= y0) & (oy < y1) & (ox >= x0) & (ox < x1)
+    w = torch.where(inbox, torch.zeros((), dtype=torch.float32), lam[:, None, None])[..., None]  # [N, Ho, Wo, 1]
+    rest = (1.0 - w) * b
+    out = (w.double() * a.double() + rest.double()).to(torch.float32).to(dtype)
+    return out.permute(0, 3, 1, 2)
+
+
+def _augment_values(src, geom, flip, scale, bias, out_hw, pad) -> torch.Tensor:
+    """``A(n)``: the fp32 values ``[N, Ho, Wo, 3]`` of the plain definition."""
     n, hs, ws, _ = src.shape
     ho, wo = out_hw
     f32 = torch.float32
@@ -143,8 +223,7 @@ def _augment_torch(src, geom, flip, scale, bias, out_hw, dtype, pad) -> torch.Te
     blend = (((1 - fy) * (1 - fx)) * tap(y0, x0, my0, mx0) + ((1 - fy) * fx) * tap(y0, x1, my0, mx1)) \
         + ((fy * (1 - fx)) * tap(y1, x0, my1, mx0) + (fy * fx) * tap(y1, x1, my1, mx1))
     # fmaf: the fp32 x fp32 product is exact in float64; with integer geometry so is the sum (one rounding)
-    out = (blend.double() * scale.double() + bias.double()).to(f32).to(dtype)
-    return out.permute(0, 3, 1, 2)
+    return (blend.double() * scale.double() + bias.double()).to(f32)
 
 
 def boxes_to_geom(y0, x0, h, w, out_hw: Tuple[int, int]) -> torch.Tensor:
@@ -231,3 +310,76 @@ class AugmentParams:
         """``(geom fp32 [n, 4], flip uint8 [n])`` of batch ``step``, on the host."""
         y0, x0, h, w, flip = self.boxes(step, n)
         return boxes_to_geom(y0, x0, h, w, self.out_hw), flip
+
+
+class MixParams:
+    """Per-batch Mixup / CutMix parameters: ``params(step, n)`` is a pure function of ``(seed, stream, step)``.
+
+    Like :class:`AugmentParams` every call seeds a private ``torch.Generator`` and never touches a global RNG; the
+    seed is mixed differently, so the crops and flips of a step are the same with and without mixing. Per batch:
+    one mode (CutMix with probability ``switch_prob`` when both alphas are > 0, else the one that is set), one
+    ``lam0 ~ Beta(alpha, alpha)`` of that mode (the ratio of two seeded Gamma draws) and ``partner = randperm(n)``.
+
+    * Mixup: ``lam = target_lam = lam0``, empty boxes, ``blend = True``.
+    * CutMix: a box of ``int(Ho r) x int(Wo r)``, ``r = sqrt(1 - lam0)``, around a centre uniform over the output
+      grid, clipped to it; ``lam = 1``, ``target_lam = 1 - box area / (Ho Wo)`` (float64, rounded to fp32),
+      ``blend = False``.
+
+    The arrays are per sample, filled with the batch's values: :func:`augment_mix` and
+    :func:`~distributed_learning_amd.ops.loss.cross_entropy_mix` take per-sample values.
+    """
+
+    def __init__(self, out_hw: Tuple[int, int], mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, seed: int = 1234,
+                 stream: int = 0, switch_prob: float = 0.5):
+        self.out_hw = (int(out_hw[0]), int(out_hw[1]))
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.switch_prob = float(switch_prob)
+        if min(self.out_hw) < 1:
+            raise ValueError(f"bad output size {out_hw}")
+        if not (self.mixup_alpha >= 0.0 and self.cutmix_alpha >= 0.0):
+            raise ValueError(f"mixup_alpha and cutmix_alpha must be >= 0, got {mixup_alpha} and {cutmix_alpha}")
+        if self.mixup_alpha == 0.0 and self.cutmix_alpha == 0.0:
+            raise ValueError("MixParams needs mixup_alpha > 0 or cutmix_alpha > 0")
+        if not 0.0 <= self.switch_prob <= 1.0:
+            raise ValueError(f"switch_prob must be in [0, 1], got {switch_prob}")
+        self.seed, self.stream = int(seed), int(stream)
+
+    def _generator(self, step: int) -> torch.Generator:
+        s = (((self.seed * 998_244_353 + self.stream) * 4_294_967_311 + int(step)) ^ 0x5DEECE66D) % (1 << 63)
+        return torch.Generator().manual_seed(s)
+
+    def draw(self, step: int) -> Tuple[bool, float]:
+        """``(cutmix, lam0)`` of batch ``step``: the mode and the Beta draw, before any box is cut."""
+        return self._draw(self._generator(step))
+
+    def _draw(self, g: torch.Generator) -> Tuple[bool, float]:
+        u = float(torch.rand(1, generator=g, dtype=torch.float64))
+        if self.mixup_alpha > 0.0 and self.cutmix_alpha > 0.0:
+            cutmix = u < self.switch_prob
+        else:
+            cutmix = self.cutmix_alpha > 0.0
+        alpha = self.cutmix_alpha if cutmix else self.mixup_alpha
+        ga, gb = torch._standard_gamma(torch.full((2,), alpha, dtype=torch.float64), generator=g).tolist()
+        lam0 = ga / (ga + gb) if ga + gb > 0.0 else 0.5  # both draws underflowed: the distribution's mean
+        return cutmix, lam0
+
+    def params(self, step: int, n: int):
+        """``(partner int32 [n], lam fp32 [n], box int32 [n, 4], target_lam fp32 [n], blend)`` of batch ``step``,
+        on the host: the first three and ``blend`` for :func:`augment_mix`, ``target_lam`` for the loss."""
+        g = self._generator(step)
+        cutmix, lam0 = self._draw(g)
+        partner = torch.randperm(n, generator=g).to(torch.int32)
+        ho, wo = self.out_hw
+        if not cutmix:
+            lam = torch.full((n,), lam0, dtype=torch.float64).to(torch.float32)
+            return partner, lam, torch.zeros((n, 4), dtype=torch.int32), lam.clone(), True
+        cy = int(torch.randint(0, ho, (1,), generator=g))
+        cx = int(torch.randint(0, wo, (1,), generator=g))
+        r = math.sqrt(1.0 - lam0)
+        ch, cw = int(ho * r), int(wo * r)
+        clip = lambda v, hi: max(0, min(v, hi))  # noqa: E731
+        y0, y1 = clip(cy - ch // 2, ho), clip(cy + ch // 2, ho)
+        x0, x1 = clip(cx - cw // 2, wo), clip(cx + cw // 2, wo)
+        box = torch.tensor([[y0, x0, y1, x1]], dtype=torch.int32).repeat(n, 1)
+        target = torch.full((n,), 1.0 - ((y1 - y0) * (x1 - x0)) / float(ho * wo), dtype=torch.float64)
+        return partner, torch.ones(n, dtype=torch.float32), box, target.to(torch.float32), False

@@ -10,6 +10,9 @@ fixed rule, on the GPU and in the fallback alike: the target's rank is the numbe
 plus the number of equal logits with a smaller class index, and a row is top-k correct iff its rank
 is below k. Ignored rows (target outside ``[0, C)``) and rows whose target logit is NaN are never
 correct.
+
+``cross_entropy_mix`` is the same smoothed loss against a weighted target pair (Mixup / CutMix), from a third
+kernel pair: one forward and one backward pass over the logits instead of two loss calls.
 """
 from __future__ import annotations
 
@@ -101,6 +104,69 @@ def cross_entropy_with_metrics(logits: torch.Tensor, target: torch.Tensor, label
         if _ext.gpu_required():
             _ext.require()
     return _metrics_fallback(logits, target, eps, k)
+
+
+class _XEntMix(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target_a, target_b, lam, eps):
+        C = _ext.require()
+        logits, lam = logits.contiguous(), lam.contiguous()
+        target_a, target_b = target_a.contiguous(), target_b.contiguous()
+        stats, ws = C.xent_mix_fwd(logits, target_a, target_b, lam, eps)
+        ctx.save_for_backward(logits, target_a, target_b, lam, ws, stats)
+        ctx.eps = eps
+        return ws[-1]  # stats[0] / stats[1], divided by the batch kernel
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target_a, target_b, lam, ws, stats = ctx.saved_tensors
+        C = _ext.require()
+        d = C.xent_mix_bwd(logits, target_a, target_b, lam, ws, stats, gout.reshape(1), ctx.eps)
+        return d, None, None, None, None
+
+
+def _mix_fallback(logits: torch.Tensor, target_a: torch.Tensor, target_b: torch.Tensor, lam: torch.Tensor,
+                  eps: float) -> torch.Tensor:
+    """The pair-target kernels' semantics in plain torch (CPU tensors, unsupported dtypes, no extension)."""
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    C = x.shape[1]
+    valid = (target_a >= 0) & (target_a < C) & (target_b >= 0) & (target_b < C)
+    ta = torch.where(valid, target_a, torch.zeros_like(target_a))
+    tb = torch.where(valid, target_b, torch.zeros_like(target_b))
+    wa = lam.to(x.dtype)
+    wb = 1.0 - wa
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    # a term whose weight is exactly 0 is left out: a -inf logit there adds nothing
+    xt = torch.where(wa != 0, wa * x.gather(1, ta[:, None]).squeeze(1), zero) \
+        + torch.where(wb != 0, wb * x.gather(1, tb[:, None]).squeeze(1), zero)
+    row = torch.logsumexp(x, dim=1) - (1.0 - eps) * xt
+    if eps > 0:
+        row = row - (eps / C) * x.sum(dim=1)
+    row = torch.where(valid, row, torch.zeros_like(row))
+    return row.sum() / valid.sum().to(row.dtype)
+
+
+def cross_entropy_mix(logits: torch.Tensor, target_a: torch.Tensor, target_b: torch.Tensor, lam: torch.Tensor,
+                      label_smoothing: float = 0.0) -> torch.Tensor:
+    """Mean label-smoothed cross-entropy of ``[B, C]`` logits against the target pair of Mixup / CutMix: row
+    ``i`` is ``lam[i] * CE(x_i, target_a[i]) + (1 - lam[i]) * CE(x_i, target_b[i])`` computed in one pass,
+    ``lse - (1 - eps) * (lam x[ta] + (1 - lam) x[tb]) - eps * mean(x)`` (a term whose weight is exactly 0 is
+    left out). ``lam`` is fp32 ``[B]`` on the logits' device. A row counts iff both targets are in ``[0, C)``;
+    the mean is over those rows (NaN without one). With ``lam == 1`` everywhere this is
+    :func:`cross_entropy_with_metrics`' loss for ``target_a``, bit for bit."""
+    eps = _check_smoothing(label_smoothing)
+    B = logits.shape[0] if logits.dim() == 2 else -1
+    if logits.dim() != 2 or any(t.dim() != 1 or t.shape[0] != B for t in (target_a, target_b, lam)):
+        raise ValueError(f"expected [B, C] logits and [B] targets and weights, got {tuple(logits.shape)}, "
+                         f"{tuple(target_a.shape)}, {tuple(target_b.shape)} and {tuple(lam.shape)}")
+    if lam.device != logits.device:
+        raise ValueError(f"lam must be on the logits' device {logits.device}, got {lam.device}")
+    if logits.is_cuda and logits.dtype in (torch.float32, torch.bfloat16):
+        if _ext.available():
+            return _XEntMix.apply(logits, target_a, target_b, lam.to(torch.float32), eps)
+        if _ext.gpu_required():
+            _ext.require()
+    return _mix_fallback(logits, target_a, target_b, lam, eps)
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:

@@ -21,6 +21,9 @@ Differences by design:
   is one uint8 copy plus one kernel (ops/augment.py) that crops, resamples, flips, normalises, casts and lays out
   the batch with parameters drawn from (seed, partition, batch number); evaluation uses the centre crop through
   the same kernel; without the flag nothing of it runs;
+* optional Mixup / CutMix on top of it (``--mixup_alpha``, ``--cutmix_alpha``, ``--mix_switch_prob``): the same
+  kernel pass mixes every sample with a partner (parameters from (seed, partition, batch number) as well) and the
+  loss is the pair-target ``ops.cross_entropy_mix``; without the flags nothing of it runs;
 * on GPU the step is the framework's measured headline path (the one ``bench.py`` times): native
   MFMA convolutions / FC heads and fused BN kernels, bf16 weights with fp32 master weights in the
   fused SGD (``--precision bf16``, default), on-device synthetic batches, and every gradient
@@ -45,7 +48,7 @@ from . import data as D
 from .models import get_spec
 from .ops import augment as aug
 from .ops import nn as dnn
-from .ops.loss import cross_entropy, cross_entropy_with_metrics
+from .ops.loss import cross_entropy, cross_entropy_mix, cross_entropy_with_metrics
 from .ops.optim import FusedLARS, FusedSGD, poly_warmup_lr
 from .timing import EventTimers, Timers
 from .utils.log import Level, print_d
@@ -102,6 +105,10 @@ def _augmenting(config) -> bool:
     return getattr(config, "augment", "none") != "none"
 
 
+def _mixing(config) -> bool:
+    return getattr(config, "mixup_alpha", 0.0) > 0 or getattr(config, "cutmix_alpha", 0.0) > 0
+
+
 def _augmenters(config, spec, device, prec: str, stream: int):
     """``--augment standard``: the (training, evaluation) transforms ``(raw uint8 batch on the device, batch
     number) -> model input`` in the step's dtype and layout, through ops/augment.py: random-resized crop 256 -> 224
@@ -123,8 +130,13 @@ def _augmenters(config, spec, device, prec: str, stream: int):
         p = aug.AugmentParams(kind, src_hw, out_hw, seed=config.seed, stream=stream,
                               scale_min=getattr(config, "aug_scale_min", 0.08), pad=pad)
 
-        def apply(x, batch: int):
-            x = aug.augment(x, *p.params(batch, x.shape[0]), mean, std, out_hw, dtype, pad)
+        def apply(x, batch: int, mix=None):
+            """``mix``: ``(partner, lam, box, blend)`` of :class:`~.ops.augment.MixParams` -- Mixup / CutMix in
+            the same kernel pass."""
+            if mix is None:
+                x = aug.augment(x, *p.params(batch, x.shape[0]), mean, std, out_hw, dtype, pad)
+            else:
+                x = aug.augment_mix(x, *p.params(batch, x.shape[0]), *mix[:3], mean, std, out_hw, dtype, pad, mix[3])
             return x if cl else x.contiguous()  # the fp32 reference-precision path runs NCHW
 
         return apply
@@ -133,13 +145,15 @@ def _augmenters(config, spec, device, prec: str, stream: int):
 
 
 def _config_text(config) -> str:
-    """``{exp}_config.txt``: the augmentation flags appear only when set, so a run without them writes the file it
-    always did."""
-    if _augmenting(config):
-        return str(config)
+    """``{exp}_config.txt``: the augmentation and mixing flags appear only when set, so a run without them writes
+    the file it always did."""
     shown = copy.copy(config)
-    for k in ("augment", "aug_scale_min"):
-        shown.__dict__.pop(k, None)
+    if not _augmenting(config):
+        for k in ("augment", "aug_scale_min"):
+            shown.__dict__.pop(k, None)
+    if not _mixing(config):
+        for k in ("mixup_alpha", "cutmix_alpha", "mix_switch_prob"):
+            shown.__dict__.pop(k, None)
     return str(shown)
 
 
@@ -314,6 +328,15 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             train_aug = None
         if isinstance(eval_set, D.SyntheticBatches):
             eval_aug = None
+    train_mix = None  # --mixup_alpha / --cutmix_alpha: per-batch partners, weights and boxes for train_aug and the loss
+    if _mixing(config):
+        if train_aug is None:
+            print_d("--mixup_alpha / --cutmix_alpha ignored: the mixing lives in the augmentation kernel, which "
+                    "synthetic input does not run", Level.WARNING)
+        else:
+            train_mix = aug.MixParams(tuple(spec.input_shape[1:]), config.mixup_alpha, config.cutmix_alpha,
+                                      seed=config.seed, stream=node_id * config.node_dev + worker_id,
+                                      switch_prob=getattr(config, "mix_switch_prob", 0.5))
 
     def run_eval(done: int) -> None:
         """One evaluation after ``done`` training batches: between two ``batch`` timer rows, never inside one."""
@@ -359,7 +382,13 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             timers.start("data2dev")
             x = x.to(device, non_blocking=True)
             y = y.to(device, non_blocking=True)
-            if train_aug is not None:
+            y_b = mix_lam = None
+            if train_mix is not None:
+                partner, lam, box, mix_lam, blend = train_mix.params(batch_count, x.shape[0])
+                x = train_aug(x, batch_count, (partner, lam, box, blend))
+                y_b = y.index_select(0, partner.to(device, non_blocking=True))
+                mix_lam = mix_lam.to(device, non_blocking=True)
+            elif train_aug is not None:
                 x = train_aug(x, batch_count)  # uint8 in, the step's dtype and layout out: no cast, no re-layout
             else:
                 if prec == "bf16" and x.is_floating_point() and x.dtype != torch.bfloat16:
@@ -376,7 +405,8 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             ev and ev.start("forward")
             with autocast:
                 out = model(x)
-                loss = cross_entropy(out, y, smoothing)
+                loss = cross_entropy(out, y, smoothing) if y_b is None \
+                    else cross_entropy_mix(out, y, y_b, mix_lam, smoothing)
             ev and ev.end("forward")
             timers.end("forward")
 
