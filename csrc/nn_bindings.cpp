@@ -597,6 +597,8 @@ static NtOperands nt_operands(const char* op, const at::Tensor& A, const at::Ten
   }
   if (const at::Tensor* a2 = opt(addend2)) {
     TORCH_CHECK(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && M % (H * W) == 0, op, ": addend2 needs even H, W dividing M");
+    // the epilogue decodes (n, h, w) from the output row with two mm::fdiv (exact for numerator < 2^24, divisor < 2^16)
+    TORCH_CHECK(M < (1 << 24) && H < 65536 && W < 65536, op, ": addend2 needs M < 2^24 rows and H, W < 65536 (24-bit index math)");
     TORCH_CHECK(a2->is_cuda() && a2->scalar_type() == at::kBFloat16 && a2->dim() == 4 && a2->size(1) == N &&
                     a2->size(2) == H / 2 && a2->size(3) == W / 2 && a2->size(0) == M / (H * W) &&
                     a2->is_contiguous(at::MemoryFormat::ChannelsLast),
@@ -1288,6 +1290,8 @@ void bind_nn(pybind11::module& m) {
   m.def("stem_fwd", &stem_fwd, "7x7/s2/p3 stem conv, 3 input channels (space-to-depth + MFMA implicit GEMM, BN-statistics epilogue)");
   m.def("stem_wgrad_bn", &stem_wgrad_bn,
         "stem weight gradient with the BN+ReLU+max-pool backward apply fused (the conv-output gradient never stored)");
+  m.def("stem_wgrad_bn_splits", [](int64_t N, int64_t H, int64_t W) { return stem_wgrad_bn_splits((int)N, (int)H, (int)W); },
+        "split count stem_wgrad_bn uses for a batch of N images of H x W");
   m.def("stem_wgrad", &stem_wgrad, "7x7/s2/p3 stem conv weight gradient from the folded input (packed [Cout, 256] layout)");
   m.def("gap_bwd", &gap_bwd, "NHWC global average pooling backward (channels_last dx)");
   m.def("gemm_nt", &gemm_nt, "C = A @ B^T (bf16 MFMA), optional fused column statistics", pybind11::arg("A"),

@@ -237,3 +237,22 @@ def test_fused_bn_pool_refuses_divisors_outside_the_fast_division(args, cuda):
     with pytest.raises(RuntimeError, match="bn_relu_maxpool_bwd: .*below 65536"):
         args.C.bn_relu_maxpool_bwd(dyp, ps, x, torch.zeros(56, device=cuda), None, 3, 2, 1)
     torch.cuda.synchronize()
+
+
+# ---- the stride-2 second addend: its epilogue decodes (n, h, w) from the output row by multiply-shift (mm::fdiv) ----
+# (op, n, H, W): a 65536-row image, and 2^24 rows; every argument well-formed apart from the size
+ADDEND2_REFUSED = [("gemm_nt", 1, 65536, 2), ("gemm_nt_bn", 1, 65536, 2), ("gemm_nt", 1, 2, 65536), ("gemm_nt", 1 << 22, 2, 2)]
+
+
+@pytest.mark.parametrize("op,n,h,w", ADDEND2_REFUSED)
+def test_addend2_refuses_rows_outside_the_fast_division(args, cuda, op, n, h, w):
+    m, c = n * h * w, 8
+    A, Bk = torch.zeros(m, c, dtype=BF, device=cuda), torch.zeros(c, c, dtype=BF, device=cuda)
+    a2 = torch.zeros(n, h // 2, w // 2, c, dtype=BF, device=cuda).permute(0, 3, 1, 2)  # channels_last [n, C, H/2, W/2]
+    with pytest.raises(RuntimeError, match=rf"{op}: addend2 needs .*24-bit index math"):
+        if op == "gemm_nt":
+            args.C.gemm_nt(A, Bk, False, None, True, 0, None, a2, h, w)
+        else:
+            args.C.gemm_nt_bn(A, Bk, None, True, torch.zeros(m, c, dtype=BF, device=cuda), torch.zeros(7 * c, device=cuda),
+                              None, 1, None, a2, h, w)
+    torch.cuda.synchronize()
