@@ -49,7 +49,31 @@ struct PackList {
   PackEntry e[kMaxList];
 };
 
+// Weight EMA (exponential moving average), fused into the list update kernels: slot t is the fp32 average of
+// list entry t, advanced from the fp32 value the update just stored, ema = fmaf(omd, p_new - ema, ema) with
+// omd = 1 - decay read from device memory (one fp32). Passed by value beside the list.
+struct EmaSlots {
+  float* ema[kMaxList];
+};
+// The same formula for fp32 tensors the optimizer does not step (target read only, shadow unused), and the
+// in-place exchange target <-> ema with shadow = bf16(new target) where shadow is non-null.
+struct EmaEntry {
+  float* target;
+  float* ema;
+  uint16_t* shadow;
+  int64_t numel;
+};
+struct EmaList {
+  int ntensors;
+  int32_t prefix[kMaxList + 1];
+  EmaEntry e[kMaxList];
+};
+
 int mt_chunk_elems();
+void launch_sgd_ema_list(const SgdList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
+                         bool use_momentum, const SgdParams& hp, hipStream_t stream);
+void launch_ema_update_list(const EmaList& list, int nblocks, const float* omd, hipStream_t stream);
+void launch_ema_swap_list(const EmaList& list, int nblocks, hipStream_t stream);
 void launch_sgd_list(const SgdList& list, int nblocks, int grad_dtype, bool use_momentum, const SgdParams& hp,
                      hipStream_t stream);
 void launch_pack_list(const PackList& list, int nblocks, int src_dtype, int flat_dtype, void* flat, float scale,
@@ -92,6 +116,8 @@ void launch_lars_finalize(const LarsTensor* table, int ntensors, const float* lr
                           float max_grad_norm, float* ws, hipStream_t stream);
 void launch_lars_list(const LarsList& list, int nblocks, int grad_dtype, const LarsTensor* table, const float* ws,
                       hipStream_t stream);
+void launch_lars_ema_list(const LarsList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
+                          const LarsTensor* table, const float* ws, hipStream_t stream);
 
 // ---- elementwise reductions for the collectives (reduce.hip) --------------------------------
 constexpr int kMaxReduceSrc = 8;

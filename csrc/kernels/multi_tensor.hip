@@ -13,7 +13,8 @@
 // Each 256-thread workgroup owns a 4096-element chunk of one tensor; the tensor is found by a
 // binary search over a block-prefix array (≤ 9 steps for 500 tensors). All accesses are 16-byte
 // vectors when the tensor is 16-byte aligned (bucket layouts pad every view to 64 B), with a
-// scalar tail. These ops are HBM-bound: 12 B/elem read + 8 B/elem written for fp32 SGD.
+// scalar tail. These ops are HBM-bound: 12 B/elem read + 8 B/elem written for fp32 SGD; the optional weight
+// EMA rides in the list update kernels for 4 B/elem more each way (times: profiles/ema/README.md).
 #include "dla_common.h"
 #include "dla_kernels.h"
 
@@ -37,8 +38,11 @@ __device__ __forceinline__ int find_tensor(const int32_t* __restrict__ prefix, i
 // d = g*grad_scale (+ wd*p); m = first ? d : mu*m + (1-damp)*d; d = nesterov ? d + mu*m : m;
 // p -= lr*d. Optionally writes a bf16 shadow copy of the updated parameter.
 // --------------------------------------------------------------------------------------------
-template <typename G, bool kMomentum>
-__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp);
+// kEma: the same pass also advances an fp32 exponential moving average of the updated value,
+// ev = fmaf(omd, p_new - ev, ev) with omd = 1 - decay.
+template <typename G, bool kMomentum, bool kEma = false>
+__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp,
+                                         float* ema = nullptr, float omd = 0.f);
 
 template <typename G, bool kMomentum>
 __global__ __launch_bounds__(kMTBlock) void sgd_kernel(const SgdEntry* __restrict__ entries,
@@ -56,19 +60,32 @@ __global__ __launch_bounds__(kMTBlock) void sgd_list_kernel(SgdList list, SgdPar
   sgd_body<G, kMomentum>(list.e[t], (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk, hp);
 }
 
+// The list kernel with the weight EMA: slot t of `ema` belongs to list.e[t]; omd = 1 - decay is read from
+// device memory, so a captured step follows a decay schedule between replays.
+template <typename G, bool kMomentum>
+__global__ __launch_bounds__(kMTBlock) void sgd_ema_list_kernel(SgdList list, EmaSlots ema,
+                                                                const float* __restrict__ omd, SgdParams hp) {
+  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
+  sgd_body<G, kMomentum, true>(list.e[t], (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk, hp, ema.ema[t], omd[0]);
+}
+
 // One chunk of one tensor through `update(p, g, m, p_out, m_out)`: reads p, g (fp32 or bf16) and m,
-// writes p, m and the optional bf16 shadow. Shared by the SGD and LARS update kernels.
-template <typename G, bool kMomentum, typename F>
-__device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, F update) {
+// writes p, m and the optional bf16 shadow. Shared by the SGD and LARS update kernels. kEma: also reads
+// and writes the fp32 average `ev` of the value just stored to p (never of the bf16 shadow).
+template <typename G, bool kMomentum, bool kEma = false, typename F>
+__device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, F update, float* ema = nullptr,
+                                             float omd = 0.f) {
   const int64_t n = e.numel;
   const int64_t end = min(n, chunk0 + (int64_t)kMTChunk);
   float* __restrict__ p = e.param;
   const G* __restrict__ g = reinterpret_cast<const G*>(e.grad);
   float* __restrict__ m = e.momentum;
   bf16_t* __restrict__ pb = e.param_bf16;
+  float* __restrict__ ev = ema;
 
   const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
                          (kMomentum ? reinterpret_cast<uintptr_t>(m) : 0) |
+                         (kEma ? reinterpret_cast<uintptr_t>(ev) : 0) |
                          (pb ? reinterpret_cast<uintptr_t>(pb) : 0)) & 15) == 0;
   if (aligned && end - chunk0 == kMTChunk) {
     // Fast path: full chunk, each thread 4 float4 groups strided by the block so that every
@@ -85,6 +102,8 @@ __device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, 
         gv = float4_t{bf16_to_f32(gr.x), bf16_to_f32(gr.y), bf16_to_f32(gr.z), bf16_to_f32(gr.w)};
       }
       float4_t mv = kMomentum ? *reinterpret_cast<const float4_t*>(m + i) : float4_t{0, 0, 0, 0};
+      float4_t ea{0, 0, 0, 0};
+      if constexpr (kEma) ea = *reinterpret_cast<const float4_t*>(ev + i);
       float po_[4], mo_[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < 4; ++j) update(pv[j], gv[j], mv[j], po_[j], mo_[j]);
@@ -92,6 +111,10 @@ __device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, 
       const float4_t mo{mo_[0], mo_[1], mo_[2], mo_[3]};
       *reinterpret_cast<float4_t*>(p + i) = po;
       if (kMomentum) *reinterpret_cast<float4_t*>(m + i) = mo;
+      if constexpr (kEma) {
+        *reinterpret_cast<float4_t*>(ev + i) = float4_t{fmaf(omd, po.x - ea.x, ea.x), fmaf(omd, po.y - ea.y, ea.y),
+                                                        fmaf(omd, po.z - ea.z, ea.z), fmaf(omd, po.w - ea.w, ea.w)};
+      }
       if (pb) {
         ushort4_t b{f32_to_bf16(po.x), f32_to_bf16(po.y), f32_to_bf16(po.z), f32_to_bf16(po.w)};
         *reinterpret_cast<ushort4_t*>(pb + i) = b;
@@ -104,18 +127,23 @@ __device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, 
       update(p[i], gv, kMomentum ? m[i] : 0.f, po, mo);
       p[i] = po;
       if (kMomentum) m[i] = mo;
+      if constexpr (kEma) {
+        const float ea = ev[i];
+        ev[i] = fmaf(omd, po - ea, ea);
+      }
       if (pb) pb[i] = f32_to_bf16(po);
     }
   }
 }
 
-template <typename G, bool kMomentum>
-__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp) {
+template <typename G, bool kMomentum, bool kEma>
+__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp, float* ema,
+                                         float omd) {
   const float lr = hp.lr, mu = hp.momentum, damp1 = 1.f - hp.dampening, wd = hp.weight_decay;
   const float gs = hp.grad_scale;
   const bool first = hp.first_step != 0;
   const bool nest = hp.nesterov != 0;
-  update_chunk<G, kMomentum>(e, chunk0, [&](float pv, float gv, float mv, float& po, float& mo) {
+  update_chunk<G, kMomentum, kEma>(e, chunk0, [&](float pv, float gv, float mv, float& po, float& mo) {
     float d = gv * gs;
     if (wd != 0.f) d = fmaf(wd, pv, d);
     if (kMomentum) {
@@ -123,7 +151,74 @@ __device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, cons
       d = nest ? fmaf(mu, mo, d) : mo;
     }
     po = fmaf(-lr, d, pv);
-  });
+  }, ema, omd);
+}
+
+// --------------------------------------------------------------------------------------------
+// EMA of fp32 tensors the optimizer does not step (BatchNorm running statistics), and the in-place
+// exchange of fp32 targets with their averages for evaluation. By-value lists like the updates.
+// --------------------------------------------------------------------------------------------
+// ema = fmaf(omd, target - ema, ema): 8 B/elem read + 4 B/elem written.
+__global__ __launch_bounds__(kMTBlock) void ema_update_list_kernel(EmaList list, const float* __restrict__ omd_dev) {
+  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
+  const EmaEntry& e = list.e[t];
+  const int64_t chunk0 = (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk;
+  const int64_t end = min(e.numel, chunk0 + (int64_t)kMTChunk);
+  const float* __restrict__ x = e.target;
+  float* __restrict__ ev = e.ema;
+  const float omd = omd_dev[0];
+  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ev)) & 15) == 0;
+  if (aligned && end - chunk0 == kMTChunk) {
+#pragma unroll
+    for (int k = 0; k < kMTPerThread / 4; ++k) {
+      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
+      const float4_t xv = *reinterpret_cast<const float4_t*>(x + i);
+      const float4_t ea = *reinterpret_cast<const float4_t*>(ev + i);
+      *reinterpret_cast<float4_t*>(ev + i) = float4_t{fmaf(omd, xv.x - ea.x, ea.x), fmaf(omd, xv.y - ea.y, ea.y),
+                                                      fmaf(omd, xv.z - ea.z, ea.z), fmaf(omd, xv.w - ea.w, ea.w)};
+    }
+  } else {
+    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
+      const float ea = ev[i];
+      ev[i] = fmaf(omd, x[i] - ea, ea);
+    }
+  }
+}
+
+// target <-> ema; shadow = bf16(new target) where the entry has one. Each element is read and written by one
+// thread, so the exchange needs no temporary; a second swap restores every bit (the shadow is a function of
+// its master).
+__global__ __launch_bounds__(kMTBlock) void ema_swap_list_kernel(EmaList list) {
+  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
+  const EmaEntry& e = list.e[t];
+  const int64_t chunk0 = (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk;
+  const int64_t end = min(e.numel, chunk0 + (int64_t)kMTChunk);
+  float* __restrict__ x = e.target;
+  float* __restrict__ ev = e.ema;
+  bf16_t* __restrict__ pb = e.shadow;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ev) |
+                         (pb ? reinterpret_cast<uintptr_t>(pb) : 0)) & 15) == 0;
+  if (aligned && end - chunk0 == kMTChunk) {
+#pragma unroll
+    for (int k = 0; k < kMTPerThread / 4; ++k) {
+      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
+      const float4_t xv = *reinterpret_cast<const float4_t*>(x + i);
+      const float4_t ea = *reinterpret_cast<const float4_t*>(ev + i);
+      *reinterpret_cast<float4_t*>(x + i) = ea;
+      *reinterpret_cast<float4_t*>(ev + i) = xv;
+      if (pb) {
+        ushort4_t b{f32_to_bf16(ea.x), f32_to_bf16(ea.y), f32_to_bf16(ea.z), f32_to_bf16(ea.w)};
+        *reinterpret_cast<ushort4_t*>(pb + i) = b;
+      }
+    }
+  } else {
+    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
+      const float xv = x[i], ea = ev[i];
+      x[i] = ea;
+      ev[i] = xv;
+      if (pb) pb[i] = f32_to_bf16(ea);
+    }
+  }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -228,6 +323,29 @@ void launch_sgd_list(const SgdList& list, int nblocks, int grad_dtype, bool use_
     if (use_momentum) hipLaunchKernelGGL((sgd_list_kernel<bf16_t, true>), grid, block, 0, stream, list, hp);
     else hipLaunchKernelGGL((sgd_list_kernel<bf16_t, false>), grid, block, 0, stream, list, hp);
   }
+}
+
+void launch_sgd_ema_list(const SgdList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
+                         bool use_momentum, const SgdParams& hp, hipStream_t stream) {
+  if (nblocks <= 0 || list.ntensors <= 0) return;
+  dim3 grid(nblocks), block(kMTBlock);
+  if (grad_dtype == kF32) {
+    if (use_momentum) hipLaunchKernelGGL((sgd_ema_list_kernel<float, true>), grid, block, 0, stream, list, ema, omd, hp);
+    else hipLaunchKernelGGL((sgd_ema_list_kernel<float, false>), grid, block, 0, stream, list, ema, omd, hp);
+  } else {
+    if (use_momentum) hipLaunchKernelGGL((sgd_ema_list_kernel<bf16_t, true>), grid, block, 0, stream, list, ema, omd, hp);
+    else hipLaunchKernelGGL((sgd_ema_list_kernel<bf16_t, false>), grid, block, 0, stream, list, ema, omd, hp);
+  }
+}
+
+void launch_ema_update_list(const EmaList& list, int nblocks, const float* omd, hipStream_t stream) {
+  if (nblocks <= 0 || list.ntensors <= 0) return;
+  hipLaunchKernelGGL(ema_update_list_kernel, dim3(nblocks), dim3(kMTBlock), 0, stream, list, omd);
+}
+
+void launch_ema_swap_list(const EmaList& list, int nblocks, hipStream_t stream) {
+  if (nblocks <= 0 || list.ntensors <= 0) return;
+  hipLaunchKernelGGL(ema_swap_list_kernel, dim3(nblocks), dim3(kMTBlock), 0, stream, list);
 }
 
 void launch_pack_list(const PackList& list, int nblocks, int src_dtype, int flat_dtype, void* flat, float scale,
@@ -404,20 +522,35 @@ __global__ __launch_bounds__(kFinBlock) void lars_finalize_kernel(const LarsTens
   }
 }
 
+template <typename G, bool kEma>
+__device__ __forceinline__ void lars_body(const LarsList& list, const LarsTensor* __restrict__ table,
+                                          const float* __restrict__ ws, int t, float* ema, float omd) {
+  const int row = list.tensor_base + t;
+  const float c = ws[0], llr = ws[kLarsHead + row];
+  const float wd = table[row].weight_decay, mu = table[row].momentum;
+  update_chunk<G, true, kEma>(list.l.e[t], (int64_t)(blockIdx.x - list.l.prefix[t]) * kMTChunk,
+                              [&](float pv, float gv, float mv, float& po, float& mo) {
+                                float d = gv * c;
+                                if (wd != 0.f) d = fmaf(wd, pv, d);
+                                mo = fmaf(mu, mv, llr * d);
+                                po = pv - mo;
+                              }, ema, omd);
+}
+
 template <typename G>
 __global__ __launch_bounds__(kMTBlock) void lars_list_kernel(LarsList list, const LarsTensor* __restrict__ table,
                                                              const float* __restrict__ ws) {
   const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
-  const int row = list.tensor_base + t;
-  const float c = ws[0], llr = ws[kLarsHead + row];
-  const float wd = table[row].weight_decay, mu = table[row].momentum;
-  update_chunk<G, true>(list.l.e[t], (int64_t)(blockIdx.x - list.l.prefix[t]) * kMTChunk,
-                        [&](float pv, float gv, float mv, float& po, float& mo) {
-                          float d = gv * c;
-                          if (wd != 0.f) d = fmaf(wd, pv, d);
-                          mo = fmaf(mu, mv, llr * d);
-                          po = pv - mo;
-                        });
+  lars_body<G, false>(list, table, ws, t, nullptr, 0.f);
+}
+
+template <typename G>
+__global__ __launch_bounds__(kMTBlock) void lars_ema_list_kernel(LarsList list, EmaSlots ema,
+                                                                 const float* __restrict__ omd,
+                                                                 const LarsTensor* __restrict__ table,
+                                                                 const float* __restrict__ ws) {
+  const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
+  lars_body<G, true>(list, table, ws, t, ema.ema[t], omd[0]);
 }
 
 void launch_sqsum_list(const LarsList& list, int nblocks, int grad_dtype, float* ws, int ntensors,
@@ -442,6 +575,16 @@ void launch_lars_list(const LarsList& list, int nblocks, int grad_dtype, const L
   dim3 grid(nblocks), block(kMTBlock);
   if (grad_dtype == kF32) hipLaunchKernelGGL((lars_list_kernel<float>), grid, block, 0, stream, list, table, ws);
   else hipLaunchKernelGGL((lars_list_kernel<bf16_t>), grid, block, 0, stream, list, table, ws);
+}
+
+void launch_lars_ema_list(const LarsList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
+                          const LarsTensor* table, const float* ws, hipStream_t stream) {
+  if (nblocks <= 0 || list.l.ntensors <= 0) return;
+  dim3 grid(nblocks), block(kMTBlock);
+  if (grad_dtype == kF32)
+    hipLaunchKernelGGL((lars_ema_list_kernel<float>), grid, block, 0, stream, list, ema, omd, table, ws);
+  else
+    hipLaunchKernelGGL((lars_ema_list_kernel<bf16_t>), grid, block, 0, stream, list, ema, omd, table, ws);
 }
 
 }  // namespace dla

@@ -109,10 +109,29 @@ class SgdTable {
 // ------------------------------------------------------------------------------------------
 // By-value list launches (tensor addresses may change every step).
 // ------------------------------------------------------------------------------------------
-void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std::vector<at::Tensor> moms,
-                   std::vector<at::Tensor> shadows, double lr, double momentum, double dampening, double weight_decay,
-                   bool nesterov, double grad_scale, bool first_step) {
+// Checks shared by the EMA entry points: an average is fp32, dense, on its target's device, with its target's
+// element order; omd (1 - decay) is one fp32 on that device.
+static void check_ema(const at::Tensor& e, const at::Tensor& target, size_t i, const char* op) {
+  check_dev(e, "ema");
+  TORCH_CHECK(e.scalar_type() == at::kFloat && e.device() == target.device() && e.numel() == target.numel() &&
+                  same_layout(e, target),
+              op, ": ema ", i, " must be fp32 on its target's device with the target's numel and layout");
+}
+
+static void check_omd(const at::Tensor& omd, const at::Tensor& like, const char* op) {
+  check_dev(omd, "omd");
+  TORCH_CHECK(omd.scalar_type() == at::kFloat && omd.numel() == 1 && omd.device() == like.device(), op,
+              ": omd must be a 1-element fp32 tensor on the tensors' device");
+}
+
+// emas == nullptr: the plain update, exactly sgd_step_list.
+static void sgd_step_list_impl(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                               const std::vector<at::Tensor>& moms, const std::vector<at::Tensor>& shadows,
+                               const std::vector<at::Tensor>* emas, const at::Tensor* omd, double lr, double momentum,
+                               double dampening, double weight_decay, bool nesterov, double grad_scale,
+                               bool first_step) {
   TORCH_CHECK(params.size() == grads.size(), "sgd_step_list: params/grads size mismatch");
+  TORCH_CHECK(!emas || emas->size() == params.size(), "sgd_step_list: ema list size mismatch");
   TORCH_CHECK(moms.empty() || moms.size() == params.size(), "sgd_step_list: momentum list size mismatch");
   TORCH_CHECK(shadows.empty() || shadows.size() == params.size(), "sgd_step_list: shadow list size mismatch");
   if (params.empty()) return;
@@ -125,6 +144,7 @@ void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
   // in the list raises with nothing updated
   struct Launch {
     SgdList list;
+    EmaSlots ema;
     int blocks;
   };
   std::vector<Launch> launches;
@@ -135,6 +155,7 @@ void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
     launches.push_back(cur);
     cur = Launch{};
   };
+  if (emas) check_omd(*omd, grads[0], "sgd_step_list");
   for (size_t i = 0; i < params.size(); ++i) {
     const at::Tensor& p = params[i];
     const at::Tensor& g = grads[i];
@@ -162,16 +183,100 @@ void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
                   "sgd_step_list: bad shadow");
       e.param_bf16 = reinterpret_cast<uint16_t*>(s.data_ptr());
     }
+    if (emas) check_ema((*emas)[i], p, i, "sgd_step_list");
     e.numel = p.numel();
     if (e.numel == 0) continue;
     cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    if (emas) cur.ema.ema[cur.list.ntensors] = (*emas)[i].data_ptr<float>();
     cur.list.e[cur.list.ntensors++] = e;
     cur.blocks += (int)((e.numel + chunk - 1) / chunk);
     if (cur.list.ntensors == kMaxList) flush();
   }
   flush();
   hipStream_t st = current_stream(grads[0]);
-  for (const Launch& L : launches) launch_sgd_list(L.list, L.blocks, gdt, use_m, hp, st);
+  for (const Launch& L : launches) {
+    if (emas) launch_sgd_ema_list(L.list, L.ema, omd->data_ptr<float>(), L.blocks, gdt, use_m, hp, st);
+    else launch_sgd_list(L.list, L.blocks, gdt, use_m, hp, st);
+  }
+}
+
+void sgd_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std::vector<at::Tensor> moms,
+                   std::vector<at::Tensor> shadows, double lr, double momentum, double dampening, double weight_decay,
+                   bool nesterov, double grad_scale, bool first_step) {
+  sgd_step_list_impl(params, grads, moms, shadows, nullptr, nullptr, lr, momentum, dampening, weight_decay, nesterov,
+                     grad_scale, first_step);
+}
+
+// sgd_step_list that also advances emas[i] = fmaf(omd, p_new - emas[i], emas[i]) in the same launches.
+void sgd_ema_step_list(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std::vector<at::Tensor> moms,
+                       std::vector<at::Tensor> shadows, std::vector<at::Tensor> emas, at::Tensor omd, double lr,
+                       double momentum, double dampening, double weight_decay, bool nesterov, double grad_scale,
+                       bool first_step) {
+  sgd_step_list_impl(params, grads, moms, shadows, &emas, &omd, lr, momentum, dampening, weight_decay, nesterov,
+                     grad_scale, first_step);
+}
+
+// emas[i] = fmaf(omd, srcs[i] - emas[i], emas[i]) (update) / targets[i] <-> emas[i] with shadows[i] =
+// bf16(new target) (swap): by-value lists, all launches built and checked before the first one runs.
+static void ema_list_op(const char* op, const std::vector<at::Tensor>& targets, const std::vector<at::Tensor>& emas,
+                        const std::vector<c10::optional<at::Tensor>>& shadows, const at::Tensor* omd) {
+  TORCH_CHECK(targets.size() == emas.size(), op, ": target/ema list size mismatch");
+  TORCH_CHECK(shadows.empty() || shadows.size() == targets.size(), op, ": shadow list size mismatch");
+  if (targets.empty()) return;
+  if (omd) check_omd(*omd, targets[0], op);
+  const int chunk = mt_chunk_elems();
+  struct Launch {
+    EmaList list;
+    int blocks;
+  };
+  std::vector<Launch> launches;
+  Launch cur{};
+  auto flush = [&]() {
+    if (cur.list.ntensors == 0) return;
+    cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    launches.push_back(cur);
+    cur = Launch{};
+  };
+  for (size_t i = 0; i < targets.size(); ++i) {
+    const at::Tensor& x = targets[i];
+    check_dev(x, "target");
+    TORCH_CHECK(x.scalar_type() == at::kFloat && x.device() == targets[0].device(), op, ": target ", i,
+                " must be fp32 on the list's device");
+    check_ema(emas[i], x, i, op);
+    EmaEntry e{};
+    e.target = x.data_ptr<float>();
+    e.ema = emas[i].data_ptr<float>();
+    if (!shadows.empty() && shadows[i].has_value() && shadows[i]->defined()) {
+      const at::Tensor& s = *shadows[i];
+      check_dev(s, "bf16 shadow");
+      TORCH_CHECK(s.scalar_type() == at::kBFloat16 && s.device() == x.device() && s.numel() == x.numel() &&
+                      same_layout(s, x),
+                  op, ": bad shadow ", i);
+      e.shadow = reinterpret_cast<uint16_t*>(s.data_ptr());
+    }
+    e.numel = x.numel();
+    if (e.numel == 0) continue;
+    TORCH_CHECK(cur.blocks + (e.numel + chunk - 1) / chunk < ((int64_t)1 << 30), op, ": too many chunks");
+    cur.list.prefix[cur.list.ntensors] = cur.blocks;
+    cur.list.e[cur.list.ntensors++] = e;
+    cur.blocks += (int)((e.numel + chunk - 1) / chunk);
+    if (cur.list.ntensors == kMaxList) flush();
+  }
+  flush();
+  hipStream_t st = current_stream(targets[0]);
+  for (const Launch& L : launches) {
+    if (omd) launch_ema_update_list(L.list, L.blocks, omd->data_ptr<float>(), st);
+    else launch_ema_swap_list(L.list, L.blocks, st);
+  }
+}
+
+void ema_update_list(std::vector<at::Tensor> emas, std::vector<at::Tensor> srcs, at::Tensor omd) {
+  ema_list_op("ema_update_list", srcs, emas, {}, &omd);
+}
+
+void ema_swap_list(std::vector<at::Tensor> targets, std::vector<at::Tensor> emas,
+                   std::vector<c10::optional<at::Tensor>> shadows) {
+  ema_list_op("ema_swap_list", targets, emas, shadows, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -233,8 +338,11 @@ class LarsPlan {
   // params may be empty (norms of `grads` only); moms / shadows are used by the update pass alone.
   void run(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
            const std::vector<at::Tensor>& moms, const std::vector<c10::optional<at::Tensor>>& shadows, bool update,
-           double grad_scale, double max_grad_norm) {
+           double grad_scale, double max_grad_norm, const std::vector<at::Tensor>* emas = nullptr,
+           const at::Tensor* omd = nullptr) {
     const size_t T = numels_.size();
+    TORCH_CHECK(!emas || (update && emas->size() == T), "lars: ema list size mismatch");
+    if (emas) check_omd(*omd, ws_, "lars");
     TORCH_CHECK(grads.size() == T, "lars: the plan was built for ", T, " tensors, got ", grads.size());
     TORCH_CHECK(params.empty() || params.size() == T, "lars: params/grads size mismatch");
     TORCH_CHECK(!update || (params.size() == T && moms.size() == T && lr_dev_.defined()),
@@ -244,6 +352,7 @@ class LarsPlan {
     // the launches of both passes, built once: by-value lists split at kMaxList tensors and at grad dtype changes
     struct Launch {
       LarsList list;
+      EmaSlots ema;
       int blocks, gdt;
     };
     std::vector<Launch> launches;
@@ -292,6 +401,10 @@ class LarsPlan {
                       "lars: bad shadow");
           e.param_bf16 = reinterpret_cast<uint16_t*>(s.data_ptr());
         }
+        if (emas) {
+          check_ema((*emas)[i], params[i], i, "lars");
+          cur.ema.ema[cur.list.l.ntensors] = (*emas)[i].data_ptr<float>();
+        }
       }
       cur.list.l.prefix[cur.list.l.ntensors] = cur.blocks;
       cur.list.l.e[cur.list.l.ntensors++] = e;
@@ -305,7 +418,10 @@ class LarsPlan {
     launch_lars_finalize(table(), (int)T, lr_dev_.defined() ? lr_dev_.data_ptr<float>() : nullptr, (float)grad_scale,
                          (float)max_grad_norm, ws(), st);
     if (update)
-      for (const Launch& L : launches) launch_lars_list(L.list, L.blocks, L.gdt, table(), ws(), st);
+      for (const Launch& L : launches) {
+        if (emas) launch_lars_ema_list(L.list, L.ema, omd->data_ptr<float>(), L.blocks, L.gdt, table(), ws(), st);
+        else launch_lars_list(L.list, L.blocks, L.gdt, table(), ws(), st);
+      }
     launches_ = (int)launches.size() * (update ? 2 : 1) + 1;
   }
 
@@ -321,6 +437,13 @@ void lars_step_list(LarsPlan& plan, std::vector<at::Tensor> params, std::vector<
                     std::vector<at::Tensor> moms, std::vector<c10::optional<at::Tensor>> shadows, double grad_scale,
                     double max_grad_norm) {
   plan.run(params, grads, moms, shadows, true, grad_scale, max_grad_norm);
+}
+
+// lars_step_list that also advances emas[i] from the fp32 value the update stores, in the update launches.
+void lars_ema_step_list(LarsPlan& plan, std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                        std::vector<at::Tensor> moms, std::vector<c10::optional<at::Tensor>> shadows,
+                        std::vector<at::Tensor> emas, at::Tensor omd, double grad_scale, double max_grad_norm) {
+  plan.run(params, grads, moms, shadows, true, grad_scale, max_grad_norm, &emas, &omd);
 }
 
 // (per_tensor[T], total[1]) = scale * (||t||_2 of each tensor, of all of them together), fp32.
@@ -631,6 +754,14 @@ void bind_ops(pybind11::module& m) {
       .def("last_launches", &LarsPlan::last_launches);
   m.def("lars_step_list", &lars_step_list,
         "fused LARS over by-value tensor lists: square sums, finalize (norms, clip, trust), update");
+  m.def("sgd_ema_step_list", &sgd_ema_step_list,
+        "sgd_step_list with the weight EMA in the same launches: ema = fmaf(omd, p_new - ema, ema), omd on the device");
+  m.def("lars_ema_step_list", &lars_ema_step_list, "lars_step_list with the weight EMA in the update launches");
+  m.def("ema_update_list", &ema_update_list, "emas[i] = fmaf(omd, srcs[i] - emas[i], emas[i]) over fp32 tensor lists");
+  m.def("ema_swap_list", &ema_swap_list,
+        "exchange fp32 targets with their EMAs in place; shadows[i] (bf16 or None) = bf16(new target)",
+        pybind11::arg("targets"), pybind11::arg("emas"),
+        pybind11::arg("shadows") = std::vector<c10::optional<at::Tensor>>());
   m.def("multi_tensor_l2norm", &multi_tensor_l2norm, "(per-tensor, total) L2 norms of a tensor list times scale");
   m.def("pack_list", &pack_list, "gather tensors into a flat buffer at element offsets (by-value list launch)");
   m.def("scale_", &scale_, "t *= scale");

@@ -83,6 +83,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "needs --augment standard)")
     p.add_argument("--mix_switch_prob", type=float, default=0.5,
                    help="with both alphas set: the probability that a batch uses CutMix, in [0, 1]")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="exponential moving average of the weights, advanced inside the optimizer's update kernels, "
+                        "in [0, 1) (0 = off); every evaluation then also reports the averaged model (eval_ema)")
+    p.add_argument("--ema_warmup", type=int, default=0, choices=[0, 1],
+                   help="1 = the decay of update t is min(ema_decay, (1 + t) / (10 + t))")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--master_port", type=int, default=29501)
     # MI355X options
@@ -137,6 +142,8 @@ def parse_args(argv: Optional[List[str]] = None):
         parser.error("--mixup_alpha and --cutmix_alpha must be >= 0")
     if not 0.0 <= config.mix_switch_prob <= 1.0:
         parser.error("--mix_switch_prob must be in [0, 1]")
+    if not 0.0 <= config.ema_decay < 1.0:
+        parser.error("--ema_decay must be in [0, 1)")
     if (config.mixup_alpha > 0 or config.cutmix_alpha > 0) and config.augment == "none":
         parser.error("--mixup_alpha / --cutmix_alpha need --augment standard: the mixing lives in that kernel")
     if config.augment != "none":

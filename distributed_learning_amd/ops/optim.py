@@ -14,9 +14,14 @@ FusedLARS: layer-wise adaptive rate scaling (You et al. 2017) for the large-batc
 with the norms, trust ratios and the global-norm clip computed on the device: a step is a handful
 of launches, reads nothing back to the host, and takes its learning rate from device memory so a
 captured step follows a schedule (``set_lr``). ``poly_warmup_lr`` is the usual schedule for it.
+
+Both take ``ema_decay``: an exponential moving average of the weights advanced inside the same update
+launches (one more fp32 read and write per element, no launch), ``ModelEMA`` to train with it and evaluate
+from it, ``ema_decay_at`` for its warmup. Off by default.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
@@ -24,19 +29,97 @@ import torch
 from . import _ext
 
 
+def ema_decay_at(t: int, decay: float, warmup: bool = False) -> float:
+    """The EMA decay of update number ``t`` (the number of updates before it): ``decay``, or with ``warmup``
+    ``min(decay, (1 + t) / (10 + t))`` so that the first averages follow the weights closely."""
+    return min(decay, (1 + t) / (10 + t)) if warmup else decay
+
+
 class _MasterWeightsOptimizer(torch.optim.Optimizer):
-    """What FusedSGD and FusedLARS share: fp32 master copies of low-precision parameters and a
-    ``load_state_dict`` that keeps them (and the momentum buffers) fp32."""
+    """What FusedSGD and FusedLARS share: fp32 master copies of low-precision parameters, a
+    ``load_state_dict`` that keeps them (and the momentum buffers and weight averages) fp32, and the
+    exponential moving average (EMA) of the weights.
+
+    EMA (``ema_decay`` in (0, 1); 0 = off: no state, and the native calls are the plain ones). The first
+    time a tensor is stepped ``state[p]["ema"]`` becomes an fp32 clone of its fp32 target (the master, or
+    the fp32 parameter) before the update; every step that updates the tensor then advances it by ::
+
+        ema = ema + (1 - decay) * (p_new - ema)
+
+    from the fp32 value just written, never from the bf16 shadow -- on the GPU inside the update launch
+    (one fused multiply-add: ``fmaf(1 - decay, p_new - ema, ema)``), elsewhere in torch. A tensor without
+    a gradient in a step is not stepped, and its EMA does not move. ``1 - decay`` lives in a device scalar
+    the kernels read, so a step captured in a HIP graph follows ``set_ema_decay`` calls made between
+    replays. A low-precision parameter without a master is averaged from its rounded value."""
 
     master_weights = False
+    ema_decay = 0.0
+    _ema_on = False
+    _omd_dev = None   # fp32 [1] on the parameters' device: 1 - decay
+    _omd_seen = None
+
+    def _init_ema(self, ema_decay: float) -> None:
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
+        self.ema_decay = float(ema_decay)
+        self._ema_on = ema_decay > 0
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self._ema_on
+
+    @staticmethod
+    def _omd_value(decay: float) -> float:
+        """float32(1 - decay): what the device scalar holds, as a Python float."""
+        return float(torch.tensor(1.0 - decay, dtype=torch.float32))
+
+    def set_ema_decay(self, decay: float) -> None:
+        """Set the decay of the following steps: the attribute and the device scalar the kernels read
+        (``float32(1 - decay)``). A stream-ordered fill, legal between graph replays."""
+        if not self._ema_on:
+            raise ValueError("set_ema_decay: the optimizer was built with ema_decay=0 (EMA off)")
+        if not 0.0 < decay < 1.0:
+            raise ValueError(f"ema_decay must be in (0, 1), got {decay}")
+        self.ema_decay = float(decay)
+        if self._omd_dev is not None:
+            self._omd_dev.fill_(1.0 - decay)
+            self._omd_seen = self.ema_decay
+
+    def _sync_omd(self, device) -> torch.Tensor:
+        """The device scalar, up to date with ``ema_decay``; never filled while a graph is being captured,
+        where the fill would be frozen into the graph."""
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            if self._omd_dev is None or self._omd_dev.device != device:
+                raise RuntimeError("run a step before capturing one (the EMA's device scalar is created there)")
+            return self._omd_dev
+        if self._omd_dev is None or self._omd_dev.device != device:
+            self._omd_dev = torch.zeros(1, dtype=torch.float32, device=device)
+            self._omd_seen = None
+        if self._omd_seen != self.ema_decay:
+            self._omd_dev.fill_(1.0 - self.ema_decay)
+            self._omd_seen = self.ema_decay
+        return self._omd_dev
+
+    def _ema(self, p, target):
+        """The average of ``p``, created from ``target`` (its fp32 master, or ``p``) before the first update."""
+        st = self.state[p]
+        if "ema" not in st:
+            st["ema"] = target.detach().clone() if target.dtype == torch.float32 else target.detach().float()
+        return st["ema"]
+
+    def _reference_ema(self, emas, targets) -> None:
+        """``e + omd * (p_new - e)`` in fp32 torch, after the update of ``targets``."""
+        omd = self._omd_value(self.ema_decay)
+        for e, t in zip(emas, targets):
+            e.add_((t.detach().float() - e).mul_(omd))
 
     def load_state_dict(self, state_dict):
         """torch.optim.Optimizer.load_state_dict casts floating-point state to each parameter's dtype
-        (through a policy it calls by class name); the fp32 master copies and momentum buffers of
-        bf16 parameters must stay fp32 for a bit-exact resume, so they are re-installed afterwards."""
+        (through a policy it calls by class name); the fp32 master copies, momentum buffers and weight
+        averages of bf16 parameters must stay fp32 for a bit-exact resume, so they are re-installed afterwards."""
         keep = {}
         for idx, st in state_dict.get("state", {}).items():
-            for k in ("master", "momentum_buffer"):
+            for k in ("master", "momentum_buffer", "ema"):
                 if k in st and torch.is_tensor(st[k]) and st[k].dtype == torch.float32:
                     keep[(idx, k)] = st[k]
         super().load_state_dict(state_dict)
@@ -66,13 +149,14 @@ class FusedSGD(_MasterWeightsOptimizer):
 
     def __init__(self, params, lr: float = 0.01, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, grad_scale: float = 1.0,
-                 master_weights: bool = False):
+                 master_weights: bool = False, ema_decay: float = 0.0):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                         nesterov=nesterov, grad_scale=grad_scale)
         super().__init__(params, defaults)
         self.master_weights = master_weights
+        self._init_ema(ema_decay)
         self._tables = {}
 
     @torch.no_grad()
@@ -110,22 +194,29 @@ class FusedSGD(_MasterWeightsOptimizer):
             (m is not None) or p.dtype == torch.float32 for p, m in zip(ps, masters))
         if ps[0].is_cuda and not native and _ext.gpu_required() and not _ext.available():
             _ext.require()
+        targets = [m if m is not None else p for p, m in zip(ps, masters)]
+        emas = [self._ema(p, t) for p, t in zip(ps, targets)] if self._ema_on else None
         if not native:
-            targets = [m if m is not None else p for p, m in zip(ps, masters)]
             self._reference_step(targets, [g.float() for g in gs], bufs, group, first)
+            if emas is not None:
+                self._reference_ema(emas, targets)
             for p, m in zip(ps, masters):
                 if m is not None:
                     p.copy_(m)
             return
-        fp = [m if m is not None else p for p, m in zip(ps, masters)]
+        fp = targets
         shadows = [p for p, m in zip(ps, masters) if m is not None]
         if shadows and len(shadows) != len(ps):  # mixed within a part cannot happen: grads share dtype
             raise RuntimeError("FusedSGD: mixed master/non-master parameters in one launch group")
         # By-value tensor lists in the kernel arguments (<= 32 tensors per launch): no device table,
         # so gradients may live anywhere and move every step (autograd-owned, set_to_none, views).
-        _ext.require().sgd_step_list(fp, gs, bufs if mom != 0 else [], shadows, group["lr"], mom,
-                                     group["dampening"], group["weight_decay"], group["nesterov"],
-                                     group["grad_scale"], first)
+        hyper = (group["lr"], mom, group["dampening"], group["weight_decay"], group["nesterov"], group["grad_scale"],
+                 first)
+        if emas is None:
+            _ext.require().sgd_step_list(fp, gs, bufs if mom != 0 else [], shadows, *hyper)
+        else:
+            _ext.require().sgd_ema_step_list(fp, gs, bufs if mom != 0 else [], shadows, emas,
+                                             self._sync_omd(ps[0].device), *hyper)
 
     @staticmethod
     def _reference_step(ps, gs, bufs, group, first):
@@ -207,7 +298,7 @@ class FusedLARS(_MasterWeightsOptimizer):
 
     def __init__(self, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0, eta: float = 1e-3,
                  eps: float = 0.0, exclude_bias_and_norm: bool = True, grad_scale: float = 1.0,
-                 max_grad_norm: float = 0.0, master_weights: bool = False):
+                 max_grad_norm: float = 0.0, master_weights: bool = False, ema_decay: float = 0.0):
         if lr < 0 or momentum < 0 or weight_decay < 0 or eta <= 0 or eps < 0 or max_grad_norm < 0:
             raise ValueError("FusedLARS: lr, momentum, weight_decay, eps, max_grad_norm >= 0 and eta > 0 required")
         defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=eta, eps=eps,
@@ -216,6 +307,7 @@ class FusedLARS(_MasterWeightsOptimizer):
         self.grad_scale = grad_scale
         self.max_grad_norm = max_grad_norm
         self.master_weights = master_weights
+        self._init_ema(ema_decay)
         self.last_grad_norm: Optional[torch.Tensor] = None  # device tensor [1]: G of the last step
         self._tables = {}     # participating tensors + hyper-parameters -> native plan (table, workspace)
         self._captured = []   # plans a HIP graph was captured with, kept alive outside the cache
@@ -277,6 +369,8 @@ class FusedLARS(_MasterWeightsOptimizer):
                 st["momentum_buffer"] = torch.zeros_like(p, dtype=torch.float32)
         masters = [self._master(p) for p in ps]
         bufs = [self.state[p]["momentum_buffer"] for p in ps]
+        targets = [m if m is not None else p for p, m in zip(ps, masters)]
+        emas = [self._ema(p, t) for p, t in zip(ps, targets)] if self._ema_on else None
         dev = ps[0].device
         on_gpu = all(p.is_cuda and p.grad.is_cuda for p in ps)
         native = on_gpu and _ext.available() and all(
@@ -286,6 +380,8 @@ class FusedLARS(_MasterWeightsOptimizer):
             _ext.require()
         if not native:
             self._reference_step(rows, masters, bufs, self._adapt(rows))
+            if emas is not None:
+                self._reference_ema(emas, targets)
             return loss
         self._sync_lr(dev)
         # the plan (device table + workspace) depends on which tensors take part, in which order, and on
@@ -309,10 +405,13 @@ class FusedLARS(_MasterWeightsOptimizer):
             self._tables[key] = self._tables.pop(key)  # most recently used last
         if torch.cuda.is_current_stream_capturing() and plan not in self._captured:
             self._captured.append(plan)  # a captured graph replays into this plan's memory: never freed
-        fp =[m if m is not None else p for p, m in zip(ps, masters)]
         shadows = [p if m is not None else None for p, m in zip(ps, masters)]
-        _ext.require().lars_step_list(plan, fp, [p.grad for p in ps], bufs, shadows, self.grad_scale,
-                                      self.max_grad_norm)
+        if emas is None:
+            _ext.require().lars_step_list(plan, targets, [p.grad for p in ps], bufs, shadows, self.grad_scale,
+                                          self.max_grad_norm)
+        else:
+            _ext.require().lars_ema_step_list(plan, targets, [p.grad for p in ps], bufs, shadows, emas,
+                                              self._sync_omd(dev), self.grad_scale, self.max_grad_norm)
         self.last_grad_norm = plan.grad_norm()
         self.last_launches = plan.last_launches()
         return loss
@@ -351,3 +450,126 @@ class FusedLARS(_MasterWeightsOptimizer):
                 p.copy_(master)
         self.last_grad_norm = G.reshape(1)
         self.last_launches = 0
+
+
+class ModelEMA:
+    """Training with, and evaluation from, the exponential moving average of a model's weights.
+
+    The parameter averages live in the optimizer (``FusedSGD`` / ``FusedLARS`` built with ``ema_decay > 0``, bare
+    or inside a ``DistributedOptimizer``), which advances them inside its update launches; this class adds the
+    averages of the model's floating-point buffers (BatchNorm running statistics; integer buffers such as
+    ``num_batches_tracked`` are left alone), the decay schedule, and the exchange of weights and averages for
+    evaluation. A buffer's average starts from the buffer's value at construction (or at ``reset_buffers()``).
+    """
+
+    def __init__(self, model, optimizer, decay: float, warmup: bool = False):
+        if not 0.0 < decay < 1.0:
+            raise ValueError(f"ModelEMA: decay must be in (0, 1), got {decay}")
+        self.model = getattr(model, "module", model)
+        self.optimizer = optimizer
+        self._opt = getattr(optimizer, "optimizer", optimizer)  # inside a DistributedOptimizer
+        if not getattr(self._opt, "ema_enabled", False):
+            raise ValueError("ModelEMA: build the optimizer with ema_decay > 0")
+        self.decay, self.warmup = float(decay), bool(warmup)
+        self.buffers = {}
+        self.reset_buffers()
+
+    def _float_buffers(self):
+        return [(n, b) for n, b in self.model.named_buffers() if b.is_floating_point()]
+
+    def reset_buffers(self) -> None:
+        """Start every buffer average from the buffer's present value."""
+        self.buffers = {n: b.detach().float().clone() for n, b in self._float_buffers()}
+
+    @staticmethod
+    def _native(tensors) -> bool:
+        on_gpu = bool(tensors) and all(t.is_cuda for t in tensors)
+        if on_gpu and _ext.gpu_required() and not _ext.available():
+            _ext.require()
+        return on_gpu and _ext.available() and all(t.dtype == torch.float32 for t in tensors)
+
+    @torch.no_grad()
+    def step(self, batch: int):
+        """Set the decay of update number ``batch`` (``ema_decay_at``), step the optimizer, then advance the
+        buffer averages by the same formula."""
+        self._opt.set_ema_decay(ema_decay_at(batch, self.decay, self.warmup))
+        out = self.optimizer.step()
+        pairs = [(self.buffers[n], b) for n, b in self._float_buffers()]
+        if not pairs:
+            return out
+        emas, bufs = [e for e, _ in pairs], [b.detach() for _, b in pairs]
+        if self._native(emas + bufs):
+            _ext.require().ema_update_list(emas, bufs, self._opt._sync_omd(bufs[0].device))
+        else:
+            self._opt._reference_ema(emas, bufs)
+        return out
+
+    def _swap_lists(self):
+        """(fp32 targets, their averages, bf16 shadows or None) of everything that has an average, and the
+        low-precision parameters without a master, whose average is fp32 while they are not."""
+        rows, lowp = [], []  # rows: (target, average, shadow)
+        for p in self.model.parameters():
+            st = self._opt.state.get(p, {})
+            if "ema" not in st:
+                continue  # never stepped: the average is the weight itself
+            if "master" in st:
+                rows.append((st["master"], st["ema"], p.detach()))
+            elif p.dtype == torch.float32:
+                rows.append((p.detach(), st["ema"], None))
+            else:
+                lowp.append((p.detach(), st["ema"]))
+        for n, b in self._float_buffers():
+            if b.dtype == torch.float32:
+                rows.append((b.detach(), self.buffers[n], None))
+            else:
+                lowp.append((b.detach(), self.buffers[n]))
+        targets, emas, shadows = ([r[i] for r in rows] for i in range(3))
+        return targets, emas, shadows, lowp
+
+    @staticmethod
+    def _swap(targets, emas, shadows, native: bool) -> None:
+        if native:
+            _ext.require().ema_swap_list(targets, emas, shadows)
+            return
+        for t, e, s in zip(targets, emas, shadows):
+            keep = t.clone()
+            t.copy_(e)
+            e.copy_(keep)
+            if s is not None:
+                s.copy_(t)
+
+    @contextlib.contextmanager
+    def applied(self):
+        """Inside the context the model computes from the averages: fp32 targets (masters, fp32 parameters,
+        buffers) are exchanged in place with their averages and bf16 shadows rewritten from the new masters;
+        on exit, also when the body raises, the exchange is undone and every tensor has its bits back."""
+        with torch.no_grad():
+            targets, emas, shadows, lowp = self._swap_lists()
+            native = self._native(targets + emas)
+            stash = [t.clone() for t, _ in lowp]
+            self._swap(targets, emas, shadows, native)
+            for t, e in lowp:
+                t.copy_(e)
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self._swap(targets, emas, shadows, native)
+                for (t, _), keep in zip(lowp, stash):
+                    t.copy_(keep)
+
+    def state_dict(self) -> dict:
+        """The buffer averages (the parameter averages travel in the optimizer's state dict)."""
+        return {"buffers": {n: e.clone() for n, e in self.buffers.items()}}
+
+    def load_state_dict(self, state: dict) -> None:
+        got = state["buffers"]
+        if set(got) != set(self.buffers):
+            raise KeyError(f"ModelEMA: buffer names differ: {sorted(set(got) ^ set(self.buffers))}")
+        for n, e in self.buffers.items():
+            e.copy_(got[n])
+
+    def model_state_dict(self) -> dict:
+        """A cloned ``state_dict()`` of the averaged model, for export."""
+        with self.applied():
+            return {k: v.detach().clone() for k, v in self.model.state_dict().items()}

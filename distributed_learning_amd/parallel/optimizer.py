@@ -72,6 +72,10 @@ class DistributedOptimizer(torch.optim.Optimizer):
     def load_state_dict(self, sd):
         return self.optimizer.load_state_dict(sd)
 
+    def set_ema_decay(self, decay: float) -> None:
+        """The wrapped FusedSGD / FusedLARS weight-average decay (ops/optim.py)."""
+        self.optimizer.set_ema_decay(decay)
+
     def add_param_group(self, group):
         raise RuntimeError("DistributedOptimizer: parameter groups are fixed at construction")
 

@@ -24,6 +24,9 @@ Differences by design:
 * optional Mixup / CutMix on top of it (``--mixup_alpha``, ``--cutmix_alpha``, ``--mix_switch_prob``): the same
   kernel pass mixes every sample with a partner (parameters from (seed, partition, batch number) as well) and the
   loss is the pair-target ``ops.cross_entropy_mix``; without the flags nothing of it runs;
+* optional weight averaging (``--ema_decay``, ``--ema_warmup``): the optimizer's update kernels also advance an
+  exponential moving average of every weight (ops/optim.py ``ModelEMA``), every evaluation runs a second time
+  from the averages (``eval_ema`` lines), and checkpoints carry them; without the flag nothing of it runs;
 * on GPU the step is the framework's measured headline path (the one ``bench.py`` times): native
   MFMA convolutions / FC heads and fused BN kernels, bf16 weights with fp32 master weights in the
   fused SGD (``--precision bf16``, default), on-device synthetic batches, and every gradient
@@ -49,7 +52,7 @@ from .models import get_spec
 from .ops import augment as aug
 from .ops import nn as dnn
 from .ops.loss import cross_entropy, cross_entropy_mix, cross_entropy_with_metrics
-from .ops.optim import FusedLARS, FusedSGD, poly_warmup_lr
+from .ops.optim import FusedLARS, FusedSGD, ModelEMA, poly_warmup_lr
 from .timing import EventTimers, Timers
 from .utils.log import Level, print_d
 
@@ -145,14 +148,17 @@ def _augmenters(config, spec, device, prec: str, stream: int):
 
 
 def _config_text(config) -> str:
-    """``{exp}_config.txt``: the augmentation and mixing flags appear only when set, so a run without them writes
-    the file it always did."""
+    """``{exp}_config.txt``: the augmentation, mixing and weight-average flags appear only when set, so a run
+    without them writes the file it always did."""
     shown = copy.copy(config)
     if not _augmenting(config):
         for k in ("augment", "aug_scale_min"):
             shown.__dict__.pop(k, None)
     if not _mixing(config):
         for k in ("mixup_alpha", "cutmix_alpha", "mix_switch_prob"):
+            shown.__dict__.pop(k, None)
+    if not getattr(config, "ema_decay", 0.0) > 0:
+        for k in ("ema_decay", "ema_warmup"):
             shown.__dict__.pop(k, None)
     return str(shown)
 
@@ -217,8 +223,11 @@ def evaluate(model: nn.Module, batches, device, precision: str = "fp32", max_bat
             "samples": int(n), "k": int(topk)}
 
 
-def save_checkpoint(path: str, model: nn.Module, optimizer, step: int, extra: Optional[dict] = None) -> None:
-    """Rank-0 checkpoint: plain ``torch.save`` of state dicts (new functionality vs the reference)."""
+def save_checkpoint(path: str, model: nn.Module, optimizer, step: int, extra: Optional[dict] = None,
+                    ema: Optional[ModelEMA] = None) -> None:
+    """Rank-0 checkpoint: plain ``torch.save`` of state dicts (new functionality vs the reference). ``ema``: the
+    buffer averages go under the key ``"ema"`` (the parameter averages are optimizer state); without it the
+    checkpoint has the keys it always had."""
     if dist.is_initialized() and dist.get_rank() != 0:
         return
     inner = getattr(model, "module", model)
@@ -228,18 +237,28 @@ def save_checkpoint(path: str, model: nn.Module, optimizer, step: int, extra: Op
     # the RNG state makes a resumed run draw the same dropout masks as an uninterrupted one
     state = {"model": inner.state_dict(), "optimizer": optimizer.state_dict(), "step": step, "extra": extra or {},
              "rng": rng}
+    if ema is not None:
+        state["ema"] = ema.state_dict()
     tmp = path + ".tmp"
     torch.save(state, tmp)
     os.replace(tmp, path)
 
 
-def load_checkpoint(path: str, model: nn.Module, optimizer=None, map_location=None) -> int:
-    """Load on every rank (``weights_only=True``: tensors and plain containers only)."""
+def load_checkpoint(path: str, model: nn.Module, optimizer=None, map_location=None,
+                    ema: Optional[ModelEMA] = None) -> int:
+    """Load on every rank (``weights_only=True``: tensors and plain containers only). ``ema``: its buffer averages
+    are loaded too; from a checkpoint without any, the average starts from the loaded weights."""
     state = torch.load(path, map_location=map_location or "cpu", weights_only=True)
     inner = getattr(model, "module", model)
     inner.load_state_dict(state["model"])
     if optimizer is not None and "optimizer" in state:
         optimizer.load_state_dict(state["optimizer"])
+    if ema is not None:
+        if "ema" in state:
+            ema.load_state_dict(state["ema"])
+        else:
+            ema.reset_buffers()
+            print_d(f"{path} holds no weight average: it starts from the loaded weights", Level.INFO)
     rng = state.get("rng") or {}
     if "cpu" in rng:
         torch.set_rng_state(rng["cpu"].cpu())
@@ -250,12 +269,13 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, map_location=No
 
 def make_optimizer(config, params, master_weights: bool):
     """``--optimizer sgd`` (default): the reference's momentum SGD; ``lars``: the fused LARS."""
+    ema = dict(ema_decay=config.ema_decay) if getattr(config, "ema_decay", 0.0) > 0 else {}
     if getattr(config, "optimizer", "sgd") == "lars":
         return FusedLARS(params, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
                          eta=getattr(config, "lars_eta", 1e-3), max_grad_norm=getattr(config, "max_grad_norm", 0.0),
-                         master_weights=master_weights)
+                         master_weights=master_weights, **ema)
     return FusedSGD(params, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
-                    master_weights=master_weights)
+                    master_weights=master_weights, **ema)
 
 
 def lr_schedule(config) -> Optional[Callable[[int], float]]:
@@ -294,9 +314,12 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
     params = list(getattr(model, "module", model).parameters())
     optimizer = make_optimizer(config, params, master_weights=prec == "bf16")
     schedule = lr_schedule(config)
+    # --ema_decay: the averages of the weights (in the optimizer) and of the floating-point buffers
+    ema = ModelEMA(model, optimizer, config.ema_decay, bool(getattr(config, "ema_warmup", 0))) \
+        if getattr(config, "ema_decay", 0.0) > 0 else None
     start_step = 0
     if getattr(config, "resume", None):
-        start_step = load_checkpoint(config.resume, model, optimizer, map_location=device)
+        start_step = load_checkpoint(config.resume, model, optimizer, map_location=device, ema=ema)
         print_d(f"resumed from {config.resume} at step {start_step}", Level.INFO)
 
     os.makedirs(config.folder, exist_ok=True)
@@ -318,7 +341,7 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
     eval_batches, eval_every = int(getattr(config, "eval_batches", 0)), int(getattr(config, "eval_every", 0))
     eval_set = _eval_data_for(config, spec, device, rank, node_id, worker_id,
                               dtype=torch.bfloat16 if prec == "bf16" else torch.float32) if eval_batches > 0 else None
-    evals = []
+    evals, evals_ema = [], []
     train_aug = eval_aug = None
     if _augmenting(config):
         train_aug, eval_aug = _augmenters(config, spec, device, prec, node_id * config.node_dev + worker_id)
@@ -346,6 +369,16 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
         evals.append(r)
         with open(f"{stem}_eval.txt", "a") as f:
             f.write(f"Worker {node_id}:{worker_id} eval at batch {done}: loss {r['loss']} top1 {r['top1']} "
+                    f"top{r['k']} {r['topk']} samples {r['samples']}\n")
+        if ema is None:
+            return
+        t0 = time.time()
+        with ema.applied():  # the same evaluation from the averaged weights; they are swapped back on exit
+            r = evaluate(model, eval_set, device, prec, eval_batches, getattr(config, "topk", 5), eval_aug)
+        r["batch"], r["seconds"] = done, time.time() - t0
+        evals_ema.append(r)
+        with open(f"{stem}_eval.txt", "a") as f:
+            f.write(f"Worker {node_id}:{worker_id} eval_ema at batch {done}: loss {r['loss']} top1 {r['top1']} "
                     f"top{r['k']} {r['topk']} samples {r['samples']}\n")
 
     if eval_set is not None:
@@ -426,7 +459,10 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             ev and ev.start("optimizer_step")
             if schedule is not None:
                 set_lr(optimizer, schedule(batch_count))
-            optimizer.step()
+            if ema is not None:
+                ema.step(batch_count)  # the global batch number: a resumed run continues the decay warmup
+            else:
+                optimizer.step()
             ev and ev.end("optimizer_step")
             timers.end("optimizer_step")
 
@@ -447,7 +483,7 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
 
     if device.type == "cuda":
         torch.cuda.synchronize()
-    wall = time.time() - t_start - sum(r["seconds"] for r in evals)  # training time: evaluations taken out
+    wall = time.time() - t_start - sum(r["seconds"] for r in evals + evals_ema)  # training time: evaluations taken out
     if eval_set is not None and (not evals or evals[-1]["batch"] != batch_count):
         run_eval(batch_count)  # --eval_every 0, or a last batch that is no multiple of it
     values = torch.stack(losses).cpu().tolist() if losses else []
@@ -465,7 +501,7 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
                 f"[precision {prec}, ops backend {dnn.get_backend()}, native conv {dnn.native_conv()}]", Level.INFO)
         nconv.CALLS.clear()
     if getattr(config, "checkpoint", None):
-        save_checkpoint(config.checkpoint, model, optimizer, batch_count)
+        save_checkpoint(config.checkpoint, model, optimizer, batch_count, ema=ema)
     model.cleanup()
     if hasattr(reducer, "cleanup"):
         reducer.cleanup()
@@ -473,4 +509,6 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
               "start_step": start_step}
     if eval_set is not None:
         result["evals"] = evals
+        if ema is not None:
+            result["evals_ema"] = evals_ema
     return result
