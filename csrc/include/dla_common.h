@@ -9,6 +9,10 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "dla_dtype.h"
+
 namespace dla {
 
 constexpr int kWave = 64;
@@ -101,6 +105,23 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
   return v;
+}
+
+// Host dtype dispatch of the launchers: f(TypeTag<float>{}) for kF32, f(TypeTag<bf16_t>{}) otherwise; with a
+// flag, f(tag, std::true_type / std::false_type{}). In a generic lambda, tag_t<decltype(tag)> is the type.
+template <typename T> struct TypeTag { using type = T; };
+template <typename Tag> using tag_t = typename Tag::type;
+template <typename F>
+inline void dispatch_dtype(int dtype, F&& f) {
+  if (dtype == kF32) f(TypeTag<float>{});
+  else f(TypeTag<bf16_t>{});
+}
+template <typename F>
+inline void dispatch_dtype(int dtype, bool flag, F&& f) {
+  dispatch_dtype(dtype, [&](auto t) {
+    if (flag) f(t, std::true_type{});
+    else f(t, std::false_type{});
+  });
 }
 
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"):

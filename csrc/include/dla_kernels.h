@@ -6,19 +6,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dla_dtype.h"
+#include "dla_lists.h"
+
 namespace dla {
 
-enum DType : int { kF32 = 0, kBF16 = 1 };
-
 // ---- multi-tensor (multi_tensor.hip) --------------------------------------------------------
-struct SgdEntry {
-  float* param;
-  const void* grad;      // float* or bf16*
-  float* momentum;       // may be null when momentum == 0
-  uint16_t* param_bf16;  // optional bf16 shadow copy of the parameter (null = skip)
-  int64_t numel;
-};
-
+// The entry and by-value list structs (SgdEntry, PackEntry, EmaEntry, SgdList, PackList, EmaList, EmaSlots,
+// LarsList) and the chunk size are in dla_lists.h.
 struct SgdParams {
   float lr;
   float momentum;
@@ -29,47 +24,6 @@ struct SgdParams {
   int first_step;
 };
 
-struct PackEntry {
-  void* tensor;    // grad tensor (pack source / unpack destination)
-  int64_t numel;
-  int64_t offset;  // element offset inside the flat bucket
-};
-
-// By-value tensor lists (kernel arguments, no device table): one launch covers up to kMaxList
-// tensors; used when tensor addresses change between steps.
-constexpr int kMaxList = 32;
-struct SgdList {
-  int ntensors;
-  int32_t prefix[kMaxList + 1];
-  SgdEntry e[kMaxList];
-};
-struct PackList {
-  int ntensors;
-  int32_t prefix[kMaxList + 1];
-  PackEntry e[kMaxList];
-};
-
-// Weight EMA (exponential moving average), fused into the list update kernels: slot t is the fp32 average of
-// list entry t, advanced from the fp32 value the update just stored, ema = fmaf(omd, p_new - ema, ema) with
-// omd = 1 - decay read from device memory (one fp32). Passed by value beside the list.
-struct EmaSlots {
-  float* ema[kMaxList];
-};
-// The same formula for fp32 tensors the optimizer does not step (target read only, shadow unused), and the
-// in-place exchange target <-> ema with shadow = bf16(new target) where shadow is non-null.
-struct EmaEntry {
-  float* target;
-  float* ema;
-  uint16_t* shadow;
-  int64_t numel;
-};
-struct EmaList {
-  int ntensors;
-  int32_t prefix[kMaxList + 1];
-  EmaEntry e[kMaxList];
-};
-
-int mt_chunk_elems();
 void launch_sgd_ema_list(const SgdList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
                          bool use_momentum, const SgdParams& hp, hipStream_t stream);
 void launch_ema_update_list(const EmaList& list, int nblocks, const float* omd, hipStream_t stream);
@@ -99,11 +53,6 @@ struct LarsTensor {
   int32_t adapt;                 // 0: excluded from layer-wise scaling (trust 1, no weight decay)
   float weight_decay;            // wd_t: already 0 for an excluded tensor
   float eta, eps, momentum;
-};
-struct LarsList {
-  SgdList l;        // param may be null for the square-sum pass (norms of the grad slot only)
-  int tensor_base;  // table row of l.e[0]
-  int block_base;   // partial slot of this launch's block 0
 };
 // fp32 workspace: [0] c = grad_scale * clip, [1] G, [2] clip, [3] spare | local_lr[T] |
 // (||p_t||, ||g_t||)[T] | partials (sum p^2, sum g^2)[nblocks], 8-byte aligned

@@ -83,10 +83,10 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
 void launch_xent_fwd(const void* logits, const int64_t* target, float* ws, float* loss_out, int B, int C, int dtype,
                      hipStream_t stream) {
   dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
-  if (dtype == kF32)
-    hipLaunchKernelGGL(xent_rows_kernel<float>, grid, block, 0, stream, (const float*)logits, target, ws, B, C);
-  else
-    hipLaunchKernelGGL(xent_rows_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)logits, target, ws, B, C);
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    hipLaunchKernelGGL(xent_rows_kernel<T>, grid, block, 0, stream, (const T*)logits, target, ws, B, C);
+  });
   hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, stream, ws, loss_out, B);
 }
 
@@ -94,12 +94,11 @@ void launch_xent_bwd(const void* logits, const int64_t* target, const float* ws,
                      const float* gout, void* dlogits, int B, int C, int dtype, hipStream_t stream) {
   const int64_t total = (int64_t)B * C;
   int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
-  if (dtype == kF32)
-    hipLaunchKernelGGL(xent_bwd_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)logits, target, ws,
-                       loss_out, gout, (float*)dlogits, B, C);
-  else
-    hipLaunchKernelGGL(xent_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)logits, target, ws,
-                       loss_out, gout, (bf16_t*)dlogits, B, C);
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    hipLaunchKernelGGL(xent_bwd_kernel<T>, dim3(grid), dim3(256), 0, stream, (const T*)logits, target, ws, loss_out,
+                       gout, (T*)dlogits, B, C);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -476,20 +475,21 @@ static bool xent_rows_vectorisable(const void* p, int C, int dtype) {
   return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (pitch % 16 == 0);
 }
 
+// One wave per row: launch(T tag, kVec constant, grid, block) for the logits' dtype and layout.
+template <typename F>
+static void xent_launch_rows(int B, int dtype, bool vec, F launch) {
+  dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
+  dispatch_dtype(dtype, vec, [&](auto t, auto v) { launch(t, v, grid, block); });
+}
+
 void launch_xent_metrics_fwd(const void* logits, const int64_t* target, float* ws, float* stats, int B, int C,
                              float eps, int k, int dtype, hipStream_t stream) {
-  if (B > 0) {
-    dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
-    const bool vec = xent_rows_vectorisable(logits, C, dtype);
-#define DLA_XENT_ROWS(T, V) \
-  hipLaunchKernelGGL((xent_metric_rows_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target, ws, B, C, eps)
-    if (dtype == kF32) {
-      if (vec) DLA_XENT_ROWS(float, true); else DLA_XENT_ROWS(float, false);
-    } else {
-      if (vec) DLA_XENT_ROWS(bf16_t, true); else DLA_XENT_ROWS(bf16_t, false);
-    }
-#undef DLA_XENT_ROWS
-  }
+  if (B > 0)
+    xent_launch_rows(B, dtype, xent_rows_vectorisable(logits, C, dtype), [&](auto t, auto v, dim3 grid, dim3 block) {
+      using T = tag_t<decltype(t)>;
+      hipLaunchKernelGGL((xent_metric_rows_kernel<T, decltype(v)::value>), grid, block, 0, stream, (const T*)logits,
+                         target, ws, B, C, eps);
+    });
   hipLaunchKernelGGL(xent_stats_kernel, dim3(1), dim3(256), 0, stream, ws, stats, B, k);
 }
 
@@ -497,34 +497,22 @@ void launch_xent_smooth_bwd(const void* logits, const int64_t* target, const flo
                             const float* gout, void* dlogits, int B, int C, float eps, int dtype,
                             hipStream_t stream) {
   if (B <= 0) return;
-  dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
   const bool vec = xent_rows_vectorisable(logits, C, dtype) && xent_rows_vectorisable(dlogits, C, dtype);
-#define DLA_XENT_BWD(T, V)                                                                                         \
-  hipLaunchKernelGGL((xent_smooth_bwd_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target, ws, stats, \
-                     gout, (T*)dlogits, B, C, eps)
-  if (dtype == kF32) {
-    if (vec) DLA_XENT_BWD(float, true); else DLA_XENT_BWD(float, false);
-  } else {
-    if (vec) DLA_XENT_BWD(bf16_t, true); else DLA_XENT_BWD(bf16_t, false);
-  }
-#undef DLA_XENT_BWD
+  xent_launch_rows(B, dtype, vec, [&](auto t, auto v, dim3 grid, dim3 block) {
+    using T = tag_t<decltype(t)>;
+    hipLaunchKernelGGL((xent_smooth_bwd_kernel<T, decltype(v)::value>), grid, block, 0, stream, (const T*)logits,
+                       target, ws, stats, gout, (T*)dlogits, B, C, eps);
+  });
 }
 
 void launch_xent_mix_fwd(const void* logits, const int64_t* target_a, const int64_t* target_b, const float* lam,
                          float* ws, float* stats, int B, int C, float eps, int dtype, hipStream_t stream) {
-  if (B > 0) {
-    dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
-    const bool vec = xent_rows_vectorisable(logits, C, dtype);
-#define DLA_XENT_MIX_ROWS(T, V)                                                                                   \
-  hipLaunchKernelGGL((xent_mix_rows_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target_a, target_b, \
-                     lam, ws, B, C, eps)
-    if (dtype == kF32) {
-      if (vec) DLA_XENT_MIX_ROWS(float, true); else DLA_XENT_MIX_ROWS(float, false);
-    } else {
-      if (vec) DLA_XENT_MIX_ROWS(bf16_t, true); else DLA_XENT_MIX_ROWS(bf16_t, false);
-    }
-#undef DLA_XENT_MIX_ROWS
-  }
+  if (B > 0)
+    xent_launch_rows(B, dtype, xent_rows_vectorisable(logits, C, dtype), [&](auto t, auto v, dim3 grid, dim3 block) {
+      using T = tag_t<decltype(t)>;
+      hipLaunchKernelGGL((xent_mix_rows_kernel<T, decltype(v)::value>), grid, block, 0, stream, (const T*)logits,
+                         target_a, target_b, lam, ws, B, C, eps);
+    });
   hipLaunchKernelGGL(xent_mix_mean_kernel, dim3(1), dim3(256), 0, stream, ws, stats, B);
 }
 
@@ -532,17 +520,12 @@ void launch_xent_mix_bwd(const void* logits, const int64_t* target_a, const int6
                          const float* ws, const float* stats, const float* gout, void* dlogits, int B, int C,
                          float eps, int dtype, hipStream_t stream) {
   if (B <= 0) return;
-  dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
   const bool vec = xent_rows_vectorisable(logits, C, dtype) && xent_rows_vectorisable(dlogits, C, dtype);
-#define DLA_XENT_MIX_BWD(T, V)                                                                                   \
-  hipLaunchKernelGGL((xent_mix_bwd_kernel<T, V>), grid, block, 0, stream, (const T*)logits, target_a, target_b, \
-                     lam, ws, stats, gout, (T*)dlogits, B, C, eps)
-  if (dtype == kF32) {
-    if (vec) DLA_XENT_MIX_BWD(float, true); else DLA_XENT_MIX_BWD(float, false);
-  } else {
-    if (vec) DLA_XENT_MIX_BWD(bf16_t, true); else DLA_XENT_MIX_BWD(bf16_t, false);
-  }
-#undef DLA_XENT_MIX_BWD
+  xent_launch_rows(B, dtype, vec, [&](auto t, auto v, dim3 grid, dim3 block) {
+    using T = tag_t<decltype(t)>;
+    hipLaunchKernelGGL((xent_mix_bwd_kernel<T, decltype(v)::value>), grid, block, 0, stream, (const T*)logits,
+                       target_a, target_b, lam, ws, stats, gout, (T*)dlogits, B, C, eps);
+  });
 }
 
 }  // namespace dla

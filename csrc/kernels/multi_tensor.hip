@@ -22,7 +22,7 @@ namespace dla {
 
 constexpr int kMTBlock = 256;
 constexpr int kMTPerThread = 16;  // 4 x float4
-constexpr int kMTChunk = kMTBlock * kMTPerThread;
+static_assert(kMTChunk == kMTBlock * kMTPerThread, "the host's chunk size is one block's work");
 
 __device__ __forceinline__ int find_tensor(const int32_t* __restrict__ prefix, int ntensors, int block) {
   int lo = 0, hi = ntensors - 1;
@@ -33,6 +33,52 @@ __device__ __forceinline__ int find_tensor(const int32_t* __restrict__ prefix, i
   return lo;
 }
 
+// This block's work: elements [begin, end) of tensor t, whose entry is e; full = a whole chunk.
+template <typename E>
+struct Chunk {
+  E e;
+  int t;
+  int64_t begin, end;
+  bool full;
+};
+template <typename E>
+__device__ __forceinline__ Chunk<E> find_chunk(const int32_t* __restrict__ prefix, int ntensors,
+                                               const E* __restrict__ entries) {
+  const int t = find_tensor(prefix, ntensors, blockIdx.x);
+  const E e = entries[t];  // read before prefix[t] is needed: one wait covers the entry and the prefix
+  const int64_t begin = (int64_t)(blockIdx.x - prefix[t]) * kMTChunk;
+  const int64_t end = min(e.numel, begin + (int64_t)kMTChunk);
+  return {e, t, begin, end, end - begin == kMTChunk};
+}
+
+// Fast path (full chunk, every pointer 16-byte aligned): each thread handles 4 groups of 4 elements strided
+// by the block, so that every wave-instruction is a contiguous 1 KiB access. Otherwise element by element.
+template <typename E, typename V, typename S>
+__device__ __forceinline__ void for_chunk(const Chunk<E>& c, bool aligned, V vec4, S scalar) {
+  if (aligned && c.full) {
+#pragma unroll
+    for (int k = 0; k < kMTPerThread / 4; ++k) vec4(c.begin + ((int64_t)k * kMTBlock + threadIdx.x) * 4);
+  } else {
+    for (int64_t i = c.begin + threadIdx.x; i < c.end; i += kMTBlock) scalar(i);
+  }
+}
+
+template <typename... P>
+__device__ __forceinline__ bool aligned16(const P*... p) {  // a null pointer counts as aligned
+  return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// 4 consecutive fp32 or bf16 elements (one 16- or 8-byte access), widened to fp32.
+template <typename G>
+__device__ __forceinline__ float4_t load4_f32(const G* p) {
+  if constexpr (sizeof(G) == 4) {
+    return *reinterpret_cast<const float4_t*>(p);
+  } else {
+    const ushort4_t r = *reinterpret_cast<const ushort4_t*>(p);
+    return float4_t{bf16_to_f32(r.x), bf16_to_f32(r.y), bf16_to_f32(r.z), bf16_to_f32(r.w)};
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // SGD with momentum / nesterov / weight decay / dampening; semantics of torch.optim.SGD.
 // d = g*grad_scale (+ wd*p); m = first ? d : mu*m + (1-damp)*d; d = nesterov ? d + mu*m : m;
@@ -41,23 +87,21 @@ __device__ __forceinline__ int find_tensor(const int32_t* __restrict__ prefix, i
 // kEma: the same pass also advances an fp32 exponential moving average of the updated value,
 // ev = fmaf(omd, p_new - ev, ev) with omd = 1 - decay.
 template <typename G, bool kMomentum, bool kEma = false>
-__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp,
-                                         float* ema = nullptr, float omd = 0.f);
+__device__ __forceinline__ void sgd_body(const Chunk<SgdEntry>& c, const SgdParams& hp, float* ema = nullptr,
+                                         float omd = 0.f);
 
 template <typename G, bool kMomentum>
 __global__ __launch_bounds__(kMTBlock) void sgd_kernel(const SgdEntry* __restrict__ entries,
                                                        const int32_t* __restrict__ prefix, int ntensors,
                                                        SgdParams hp) {
-  const int t = find_tensor(prefix, ntensors, blockIdx.x);
-  sgd_body<G, kMomentum>(entries[t], (int64_t)(blockIdx.x - prefix[t]) * kMTChunk, hp);
+  sgd_body<G, kMomentum>(find_chunk(prefix, ntensors, entries), hp);
 }
 
 // Same update with the tensor list passed BY VALUE in the kernel arguments (no device table): used
 // when gradient pointers change every step (autograd-owned gradients, set_to_none zero_grad).
 template <typename G, bool kMomentum>
 __global__ __launch_bounds__(kMTBlock) void sgd_list_kernel(SgdList list, SgdParams hp) {
-  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
-  sgd_body<G, kMomentum>(list.e[t], (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk, hp);
+  sgd_body<G, kMomentum>(find_chunk(list.prefix, list.ntensors, list.e), hp);
 }
 
 // The list kernel with the weight EMA: slot t of `ema` belongs to list.e[t]; omd = 1 - decay is read from
@@ -65,85 +109,66 @@ __global__ __launch_bounds__(kMTBlock) void sgd_list_kernel(SgdList list, SgdPar
 template <typename G, bool kMomentum>
 __global__ __launch_bounds__(kMTBlock) void sgd_ema_list_kernel(SgdList list, EmaSlots ema,
                                                                 const float* __restrict__ omd, SgdParams hp) {
-  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
-  sgd_body<G, kMomentum, true>(list.e[t], (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk, hp, ema.ema[t], omd[0]);
+  const auto c = find_chunk(list.prefix, list.ntensors, list.e);
+  sgd_body<G, kMomentum, true>(c, hp, ema.ema[c.t], omd[0]);
 }
 
 // One chunk of one tensor through `update(p, g, m, p_out, m_out)`: reads p, g (fp32 or bf16) and m,
 // writes p, m and the optional bf16 shadow. Shared by the SGD and LARS update kernels. kEma: also reads
 // and writes the fp32 average `ev` of the value just stored to p (never of the bf16 shadow).
 template <typename G, bool kMomentum, bool kEma = false, typename F>
-__device__ __forceinline__ void update_chunk(const SgdEntry& e, int64_t chunk0, F update, float* ema = nullptr,
+__device__ __forceinline__ void update_chunk(const Chunk<SgdEntry>& c, F update, float* ema = nullptr,
                                              float omd = 0.f) {
-  const int64_t n = e.numel;
-  const int64_t end = min(n, chunk0 + (int64_t)kMTChunk);
-  float* __restrict__ p = e.param;
-  const G* __restrict__ g = reinterpret_cast<const G*>(e.grad);
-  float* __restrict__ m = e.momentum;
-  bf16_t* __restrict__ pb = e.param_bf16;
+  float* __restrict__ p = c.e.param;
+  const G* __restrict__ g = reinterpret_cast<const G*>(c.e.grad);
+  float* __restrict__ m = c.e.momentum;
+  bf16_t* __restrict__ pb = c.e.param_bf16;
   float* __restrict__ ev = ema;
-
-  const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
-                         (kMomentum ? reinterpret_cast<uintptr_t>(m) : 0) |
-                         (kEma ? reinterpret_cast<uintptr_t>(ev) : 0) |
-                         (pb ? reinterpret_cast<uintptr_t>(pb) : 0)) & 15) == 0;
-  if (aligned && end - chunk0 == kMTChunk) {
-    // Fast path: full chunk, each thread 4 float4 groups strided by the block so that every
-    // wave-instruction is a contiguous 1 KiB access.
+  for_chunk(
+      c, aligned16(p, g, kMomentum ? m : nullptr, kEma ? ev : nullptr, pb),
+      [&](int64_t i) {
+        float4_t pv = *reinterpret_cast<const float4_t*>(p + i);
+        float4_t gv = load4_f32(g + i);
+        float4_t mv = kMomentum ? *reinterpret_cast<const float4_t*>(m + i) : float4_t{0, 0, 0, 0};
+        float4_t ea{0, 0, 0, 0};
+        if constexpr (kEma) ea = *reinterpret_cast<const float4_t*>(ev + i);
+        float po_[4], mo_[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < kMTPerThread / 4; ++k) {
-      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
-      float4_t pv = *reinterpret_cast<const float4_t*>(p + i);
-      float4_t gv;
-      if constexpr (sizeof(G) == 4) {
-        gv = *reinterpret_cast<const float4_t*>(reinterpret_cast<const float*>(g) + i);
-      } else {
-        ushort4_t gr = *reinterpret_cast<const ushort4_t*>(reinterpret_cast<const bf16_t*>(g) + i);
-        gv = float4_t{bf16_to_f32(gr.x), bf16_to_f32(gr.y), bf16_to_f32(gr.z), bf16_to_f32(gr.w)};
-      }
-      float4_t mv = kMomentum ? *reinterpret_cast<const float4_t*>(m + i) : float4_t{0, 0, 0, 0};
-      float4_t ea{0, 0, 0, 0};
-      if constexpr (kEma) ea = *reinterpret_cast<const float4_t*>(ev + i);
-      float po_[4], mo_[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) update(pv[j], gv[j], mv[j], po_[j], mo_[j]);
-      const float4_t po{po_[0], po_[1], po_[2], po_[3]};
-      const float4_t mo{mo_[0], mo_[1], mo_[2], mo_[3]};
-      *reinterpret_cast<float4_t*>(p + i) = po;
-      if (kMomentum) *reinterpret_cast<float4_t*>(m + i) = mo;
-      if constexpr (kEma) {
-        *reinterpret_cast<float4_t*>(ev + i) = float4_t{fmaf(omd, po.x - ea.x, ea.x), fmaf(omd, po.y - ea.y, ea.y),
-                                                        fmaf(omd, po.z - ea.z, ea.z), fmaf(omd, po.w - ea.w, ea.w)};
-      }
-      if (pb) {
-        ushort4_t b{f32_to_bf16(po.x), f32_to_bf16(po.y), f32_to_bf16(po.z), f32_to_bf16(po.w)};
-        *reinterpret_cast<ushort4_t*>(pb + i) = b;
-      }
-    }
-  } else {
-    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
-      float po, mo = 0.f;
-      const float gv = Cvt<G>::to_f32(g[i]);
-      update(p[i], gv, kMomentum ? m[i] : 0.f, po, mo);
-      p[i] = po;
-      if (kMomentum) m[i] = mo;
-      if constexpr (kEma) {
-        const float ea = ev[i];
-        ev[i] = fmaf(omd, po - ea, ea);
-      }
-      if (pb) pb[i] = f32_to_bf16(po);
-    }
-  }
+        for (int j = 0; j < 4; ++j) update(pv[j], gv[j], mv[j], po_[j], mo_[j]);
+        const float4_t po{po_[0], po_[1], po_[2], po_[3]};
+        const float4_t mo{mo_[0], mo_[1], mo_[2], mo_[3]};
+        *reinterpret_cast<float4_t*>(p + i) = po;
+        if (kMomentum) *reinterpret_cast<float4_t*>(m + i) = mo;
+        if constexpr (kEma) {
+          *reinterpret_cast<float4_t*>(ev + i) = float4_t{fmaf(omd, po.x - ea.x, ea.x), fmaf(omd, po.y - ea.y, ea.y),
+                                                          fmaf(omd, po.z - ea.z, ea.z), fmaf(omd, po.w - ea.w, ea.w)};
+        }
+        if (pb) {
+          ushort4_t b{f32_to_bf16(po.x), f32_to_bf16(po.y), f32_to_bf16(po.z), f32_to_bf16(po.w)};
+          *reinterpret_cast<ushort4_t*>(pb + i) = b;
+        }
+      },
+      [&](int64_t i) {
+        float po, mo = 0.f;
+        const float gv = Cvt<G>::to_f32(g[i]);
+        update(p[i], gv, kMomentum ? m[i] : 0.f, po, mo);
+        p[i] = po;
+        if (kMomentum) m[i] = mo;
+        if constexpr (kEma) {
+          const float ea = ev[i];
+          ev[i] = fmaf(omd, po - ea, ea);
+        }
+        if (pb) pb[i] = f32_to_bf16(po);
+      });
 }
 
 template <typename G, bool kMomentum, bool kEma>
-__device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, const SgdParams& hp, float* ema,
-                                         float omd) {
+__device__ __forceinline__ void sgd_body(const Chunk<SgdEntry>& c, const SgdParams& hp, float* ema, float omd) {
   const float lr = hp.lr, mu = hp.momentum, damp1 = 1.f - hp.dampening, wd = hp.weight_decay;
   const float gs = hp.grad_scale;
   const bool first = hp.first_step != 0;
   const bool nest = hp.nesterov != 0;
-  update_chunk<G, kMomentum, kEma>(e, chunk0, [&](float pv, float gv, float mv, float& po, float& mo) {
+  update_chunk<G, kMomentum, kEma>(c, [&](float pv, float gv, float mv, float& po, float& mo) {
     float d = gv * gs;
     if (wd != 0.f) d = fmaf(wd, pv, d);
     if (kMomentum) {
@@ -160,65 +185,50 @@ __device__ __forceinline__ void sgd_body(const SgdEntry& e, int64_t chunk0, cons
 // --------------------------------------------------------------------------------------------
 // ema = fmaf(omd, target - ema, ema): 8 B/elem read + 4 B/elem written.
 __global__ __launch_bounds__(kMTBlock) void ema_update_list_kernel(EmaList list, const float* __restrict__ omd_dev) {
-  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
-  const EmaEntry& e = list.e[t];
-  const int64_t chunk0 = (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk;
-  const int64_t end = min(e.numel, chunk0 + (int64_t)kMTChunk);
-  const float* __restrict__ x = e.target;
-  float* __restrict__ ev = e.ema;
+  const auto c = find_chunk(list.prefix, list.ntensors, list.e);
+  const float* __restrict__ x = c.e.target;
+  float* __restrict__ ev = c.e.ema;
   const float omd = omd_dev[0];
-  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ev)) & 15) == 0;
-  if (aligned && end - chunk0 == kMTChunk) {
-#pragma unroll
-    for (int k = 0; k < kMTPerThread / 4; ++k) {
-      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
-      const float4_t xv = *reinterpret_cast<const float4_t*>(x + i);
-      const float4_t ea = *reinterpret_cast<const float4_t*>(ev + i);
-      *reinterpret_cast<float4_t*>(ev + i) = float4_t{fmaf(omd, xv.x - ea.x, ea.x), fmaf(omd, xv.y - ea.y, ea.y),
-                                                      fmaf(omd, xv.z - ea.z, ea.z), fmaf(omd, xv.w - ea.w, ea.w)};
-    }
-  } else {
-    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
-      const float ea = ev[i];
-      ev[i] = fmaf(omd, x[i] - ea, ea);
-    }
-  }
+  for_chunk(
+      c, aligned16(x, ev),
+      [&](int64_t i) {
+        const float4_t xv = *reinterpret_cast<const float4_t*>(x + i);
+        const float4_t ea = *reinterpret_cast<const float4_t*>(ev + i);
+        *reinterpret_cast<float4_t*>(ev + i) = float4_t{fmaf(omd, xv.x - ea.x, ea.x), fmaf(omd, xv.y - ea.y, ea.y),
+                                                        fmaf(omd, xv.z - ea.z, ea.z), fmaf(omd, xv.w - ea.w, ea.w)};
+      },
+      [&](int64_t i) {
+        const float ea = ev[i];
+        ev[i] = fmaf(omd, x[i] - ea, ea);
+      });
 }
 
 // target <-> ema; shadow = bf16(new target) where the entry has one. Each element is read and written by one
 // thread, so the exchange needs no temporary; a second swap restores every bit (the shadow is a function of
 // its master).
 __global__ __launch_bounds__(kMTBlock) void ema_swap_list_kernel(EmaList list) {
-  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
-  const EmaEntry& e = list.e[t];
-  const int64_t chunk0 = (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk;
-  const int64_t end = min(e.numel, chunk0 + (int64_t)kMTChunk);
-  float* __restrict__ x = e.target;
-  float* __restrict__ ev = e.ema;
-  bf16_t* __restrict__ pb = e.shadow;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ev) |
-                         (pb ? reinterpret_cast<uintptr_t>(pb) : 0)) & 15) == 0;
-  if (aligned && end - chunk0 == kMTChunk) {
-#pragma unroll
-    for (int k = 0; k < kMTPerThread / 4; ++k) {
-      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
-      const float4_t xv = *reinterpret_cast<const float4_t*>(x + i);
-      const float4_t ea = *reinterpret_cast<const float4_t*>(ev + i);
-      *reinterpret_cast<float4_t*>(x + i) = ea;
-      *reinterpret_cast<float4_t*>(ev + i) = xv;
-      if (pb) {
-        ushort4_t b{f32_to_bf16(ea.x), f32_to_bf16(ea.y), f32_to_bf16(ea.z), f32_to_bf16(ea.w)};
-        *reinterpret_cast<ushort4_t*>(pb + i) = b;
-      }
-    }
-  } else {
-    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
-      const float xv = x[i], ea = ev[i];
-      x[i] = ea;
-      ev[i] = xv;
-      if (pb) pb[i] = f32_to_bf16(ea);
-    }
-  }
+  const auto c = find_chunk(list.prefix, list.ntensors, list.e);
+  float* __restrict__ x = c.e.target;
+  float* __restrict__ ev = c.e.ema;
+  bf16_t* __restrict__ pb = c.e.shadow;
+  for_chunk(
+      c, aligned16(x, ev, pb),
+      [&](int64_t i) {
+        const float4_t xv = *reinterpret_cast<const float4_t*>(x + i);
+        const float4_t ea = *reinterpret_cast<const float4_t*>(ev + i);
+        *reinterpret_cast<float4_t*>(x + i) = ea;
+        *reinterpret_cast<float4_t*>(ev + i) = xv;
+        if (pb) {
+          ushort4_t b{f32_to_bf16(ea.x), f32_to_bf16(ea.y), f32_to_bf16(ea.z), f32_to_bf16(ea.w)};
+          *reinterpret_cast<ushort4_t*>(pb + i) = b;
+        }
+      },
+      [&](int64_t i) {
+        const float xv = x[i], ea = ev[i];
+        x[i] = ea;
+        ev[i] = xv;
+        if (pb) pb[i] = f32_to_bf16(ea);
+      });
 }
 
 // --------------------------------------------------------------------------------------------
@@ -227,71 +237,43 @@ __global__ __launch_bounds__(kMTBlock) void ema_swap_list_kernel(EmaList list) {
 // --------------------------------------------------------------------------------------------
 template <typename S, typename D>
 __device__ __forceinline__ void copy_scale_range(const S* __restrict__ src, D* __restrict__ dst,
-                                                 int64_t begin, int64_t end, float scale, bool full) {
-  const bool aligned = ((reinterpret_cast<uintptr_t>(src + begin) |
-                         reinterpret_cast<uintptr_t>(dst + begin)) & 15) == 0;
-  if (full && aligned) {
-#pragma unroll
-    for (int k = 0; k < kMTPerThread / 4; ++k) {
-      const int64_t i = begin + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
-      float v[4];
-      if constexpr (sizeof(S) == 4) {
-        float4_t x = *reinterpret_cast<const float4_t*>(reinterpret_cast<const float*>(src) + i);
-        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-      } else {
-        ushort4_t x = *reinterpret_cast<const ushort4_t*>(reinterpret_cast<const bf16_t*>(src) + i);
-        v[0] = bf16_to_f32(x.x); v[1] = bf16_to_f32(x.y); v[2] = bf16_to_f32(x.z); v[3] = bf16_to_f32(x.w);
-      }
-      if constexpr (sizeof(D) == 4) {
-        *reinterpret_cast<float4_t*>(reinterpret_cast<float*>(dst) + i) =
-            float4_t{v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale};
-      } else {
-        *reinterpret_cast<ushort4_t*>(reinterpret_cast<bf16_t*>(dst) + i) =
-            ushort4_t{f32_to_bf16(v[0] * scale), f32_to_bf16(v[1] * scale), f32_to_bf16(v[2] * scale),
-                      f32_to_bf16(v[3] * scale)};
-      }
-    }
-  } else {
-    for (int64_t i = begin + threadIdx.x; i < end; i += kMTBlock) {
-      dst[i] = Cvt<D>::from_f32(Cvt<S>::to_f32(src[i]) * scale);
-    }
-  }
+                                                 const Chunk<PackEntry>& c, float scale) {
+  for_chunk(
+      c, aligned16(src, dst),
+      [&](int64_t i) {
+        const float4_t v = load4_f32(src + i);
+        if constexpr (sizeof(D) == 4) {
+          *reinterpret_cast<float4_t*>(reinterpret_cast<float*>(dst) + i) =
+              float4_t{v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale};
+        } else {
+          *reinterpret_cast<ushort4_t*>(reinterpret_cast<bf16_t*>(dst) + i) =
+              ushort4_t{f32_to_bf16(v[0] * scale), f32_to_bf16(v[1] * scale), f32_to_bf16(v[2] * scale),
+                        f32_to_bf16(v[3] * scale)};
+        }
+      },
+      [&](int64_t i) { dst[i] = Cvt<D>::from_f32(Cvt<S>::to_f32(src[i]) * scale); });
 }
 
 template <typename S, typename D>
 __global__ __launch_bounds__(kMTBlock) void pack_kernel(const PackEntry* __restrict__ entries,
                                                         const int32_t* __restrict__ prefix, int ntensors,
                                                         void* __restrict__ flat, float scale) {
-  const int t = find_tensor(prefix, ntensors, blockIdx.x);
-  const PackEntry e = entries[t];
-  const int64_t c0 = (int64_t)(blockIdx.x - prefix[t]) * kMTChunk;
-  const int64_t end = min(e.numel, c0 + (int64_t)kMTChunk);
-  const S* src = reinterpret_cast<const S*>(e.tensor);
-  D* dst = reinterpret_cast<D*>(flat) + e.offset;
-  copy_scale_range<S, D>(src, dst, c0, end, scale, end - c0 == kMTChunk);
+  const auto c = find_chunk(prefix, ntensors, entries);
+  copy_scale_range(reinterpret_cast<const S*>(c.e.tensor), reinterpret_cast<D*>(flat) + c.e.offset, c, scale);
 }
 
 template <typename S, typename D>
 __global__ __launch_bounds__(kMTBlock) void pack_list_kernel(PackList list, void* __restrict__ flat, float scale) {
-  const int t = find_tensor(list.prefix, list.ntensors, blockIdx.x);
-  const PackEntry& e = list.e[t];
-  const int64_t c0 = (int64_t)(blockIdx.x - list.prefix[t]) * kMTChunk;
-  const int64_t end = min(e.numel, c0 + (int64_t)kMTChunk);
-  copy_scale_range<S, D>(reinterpret_cast<const S*>(e.tensor), reinterpret_cast<D*>(flat) + e.offset, c0, end, scale,
-                         end - c0 == kMTChunk);
+  const auto c = find_chunk(list.prefix, list.ntensors, list.e);
+  copy_scale_range(reinterpret_cast<const S*>(c.e.tensor), reinterpret_cast<D*>(flat) + c.e.offset, c, scale);
 }
 
 template <typename S, typename D>
 __global__ __launch_bounds__(kMTBlock) void unpack_kernel(const PackEntry* __restrict__ entries,
                                                           const int32_t* __restrict__ prefix, int ntensors,
                                                           const void* __restrict__ flat, float scale) {
-  const int t = find_tensor(prefix, ntensors, blockIdx.x);
-  const PackEntry e = entries[t];
-  const int64_t c0 = (int64_t)(blockIdx.x - prefix[t]) * kMTChunk;
-  const int64_t end = min(e.numel, c0 + (int64_t)kMTChunk);
-  const S* src = reinterpret_cast<const S*>(flat) + e.offset;
-  D* dst = reinterpret_cast<D*>(e.tensor);
-  copy_scale_range<S, D>(src, dst, c0, end, scale, end - c0 == kMTChunk);
+  const auto c = find_chunk(prefix, ntensors, entries);
+  copy_scale_range(reinterpret_cast<const S*>(flat) + c.e.offset, reinterpret_cast<D*>(c.e.tensor), c, scale);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -300,42 +282,28 @@ __global__ __launch_bounds__(kMTBlock) void unpack_kernel(const PackEntry* __res
 void launch_sgd(const SgdEntry* entries, const int32_t* prefix, int ntensors, int nblocks, int grad_dtype,
                 bool use_momentum, const SgdParams& hp, hipStream_t stream) {
   if (nblocks <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (grad_dtype == kF32) {
-    if (use_momentum) hipLaunchKernelGGL((sgd_kernel<float, true>), grid, block, 0, stream, entries, prefix, ntensors, hp);
-    else hipLaunchKernelGGL((sgd_kernel<float, false>), grid, block, 0, stream, entries, prefix, ntensors, hp);
-  } else {
-    if (use_momentum) hipLaunchKernelGGL((sgd_kernel<bf16_t, true>), grid, block, 0, stream, entries, prefix, ntensors, hp);
-    else hipLaunchKernelGGL((sgd_kernel<bf16_t, false>), grid, block, 0, stream, entries, prefix, ntensors, hp);
-  }
+  dispatch_dtype(grad_dtype, use_momentum, [&](auto g, auto m) {
+    hipLaunchKernelGGL((sgd_kernel<tag_t<decltype(g)>, decltype(m)::value>), dim3(nblocks), dim3(kMTBlock), 0, stream,
+                       entries, prefix, ntensors, hp);
+  });
 }
-
-int mt_chunk_elems() { return kMTChunk; }
 
 void launch_sgd_list(const SgdList& list, int nblocks, int grad_dtype, bool use_momentum, const SgdParams& hp,
                      hipStream_t stream) {
   if (nblocks <= 0 || list.ntensors <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (grad_dtype == kF32) {
-    if (use_momentum) hipLaunchKernelGGL((sgd_list_kernel<float, true>), grid, block, 0, stream, list, hp);
-    else hipLaunchKernelGGL((sgd_list_kernel<float, false>), grid, block, 0, stream, list, hp);
-  } else {
-    if (use_momentum) hipLaunchKernelGGL((sgd_list_kernel<bf16_t, true>), grid, block, 0, stream, list, hp);
-    else hipLaunchKernelGGL((sgd_list_kernel<bf16_t, false>), grid, block, 0, stream, list, hp);
-  }
+  dispatch_dtype(grad_dtype, use_momentum, [&](auto g, auto m) {
+    hipLaunchKernelGGL((sgd_list_kernel<tag_t<decltype(g)>, decltype(m)::value>), dim3(nblocks), dim3(kMTBlock), 0,
+                       stream, list, hp);
+  });
 }
 
 void launch_sgd_ema_list(const SgdList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
                          bool use_momentum, const SgdParams& hp, hipStream_t stream) {
   if (nblocks <= 0 || list.ntensors <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (grad_dtype == kF32) {
-    if (use_momentum) hipLaunchKernelGGL((sgd_ema_list_kernel<float, true>), grid, block, 0, stream, list, ema, omd, hp);
-    else hipLaunchKernelGGL((sgd_ema_list_kernel<float, false>), grid, block, 0, stream, list, ema, omd, hp);
-  } else {
-    if (use_momentum) hipLaunchKernelGGL((sgd_ema_list_kernel<bf16_t, true>), grid, block, 0, stream, list, ema, omd, hp);
-    else hipLaunchKernelGGL((sgd_ema_list_kernel<bf16_t, false>), grid, block, 0, stream, list, ema, omd, hp);
-  }
+  dispatch_dtype(grad_dtype, use_momentum, [&](auto g, auto m) {
+    hipLaunchKernelGGL((sgd_ema_list_kernel<tag_t<decltype(g)>, decltype(m)::value>), dim3(nblocks), dim3(kMTBlock),
+                       0, stream, list, ema, omd, hp);
+  });
 }
 
 void launch_ema_update_list(const EmaList& list, int nblocks, const float* omd, hipStream_t stream) {
@@ -348,46 +316,37 @@ void launch_ema_swap_list(const EmaList& list, int nblocks, hipStream_t stream) 
   hipLaunchKernelGGL(ema_swap_list_kernel, dim3(nblocks), dim3(kMTBlock), 0, stream, list);
 }
 
+// f(TypeTag<S>, TypeTag<D>) for a (source, destination) dtype pair
+template <typename F>
+static void dispatch_copy(int src_dtype, int dst_dtype, F f) {
+  dispatch_dtype(src_dtype, [&](auto s) { dispatch_dtype(dst_dtype, [&](auto d) { f(s, d); }); });
+}
+
 void launch_pack_list(const PackList& list, int nblocks, int src_dtype, int flat_dtype, void* flat, float scale,
                       hipStream_t stream) {
   if (nblocks <= 0 || list.ntensors <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (src_dtype == kF32 && flat_dtype == kF32)
-    hipLaunchKernelGGL((pack_list_kernel<float, float>), grid, block, 0, stream, list, flat, scale);
-  else if (src_dtype == kF32 && flat_dtype == kBF16)
-    hipLaunchKernelGGL((pack_list_kernel<float, bf16_t>), grid, block, 0, stream, list, flat, scale);
-  else if (src_dtype == kBF16 && flat_dtype == kBF16)
-    hipLaunchKernelGGL((pack_list_kernel<bf16_t, bf16_t>), grid, block, 0, stream, list, flat, scale);
-  else
-    hipLaunchKernelGGL((pack_list_kernel<bf16_t, float>), grid, block, 0, stream, list, flat, scale);
+  dispatch_copy(src_dtype, flat_dtype, [&](auto s, auto d) {
+    hipLaunchKernelGGL((pack_list_kernel<tag_t<decltype(s)>, tag_t<decltype(d)>>), dim3(nblocks), dim3(kMTBlock), 0,
+                       stream, list, flat, scale);
+  });
 }
 
 void launch_pack(const PackEntry* entries, const int32_t* prefix, int ntensors, int nblocks, int src_dtype,
                  int flat_dtype, void* flat, float scale, hipStream_t stream) {
   if (nblocks <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (src_dtype == kF32 && flat_dtype == kF32)
-    hipLaunchKernelGGL((pack_kernel<float, float>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
-  else if (src_dtype == kF32 && flat_dtype == kBF16)
-    hipLaunchKernelGGL((pack_kernel<float, bf16_t>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
-  else if (src_dtype == kBF16 && flat_dtype == kBF16)
-    hipLaunchKernelGGL((pack_kernel<bf16_t, bf16_t>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
-  else
-    hipLaunchKernelGGL((pack_kernel<bf16_t, float>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
+  dispatch_copy(src_dtype, flat_dtype, [&](auto s, auto d) {
+    hipLaunchKernelGGL((pack_kernel<tag_t<decltype(s)>, tag_t<decltype(d)>>), dim3(nblocks), dim3(kMTBlock), 0, stream,
+                       entries, prefix, ntensors, flat, scale);
+  });
 }
 
 void launch_unpack(const PackEntry* entries, const int32_t* prefix, int ntensors, int nblocks, int flat_dtype,
                    int dst_dtype, const void* flat, float scale, hipStream_t stream) {
   if (nblocks <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (flat_dtype == kF32 && dst_dtype == kF32)
-    hipLaunchKernelGGL((unpack_kernel<float, float>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
-  else if (flat_dtype == kBF16 && dst_dtype == kF32)
-    hipLaunchKernelGGL((unpack_kernel<bf16_t, float>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
-  else if (flat_dtype == kBF16 && dst_dtype == kBF16)
-    hipLaunchKernelGGL((unpack_kernel<bf16_t, bf16_t>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
-  else
-    hipLaunchKernelGGL((unpack_kernel<float, bf16_t>), grid, block, 0, stream, entries, prefix, ntensors, flat, scale);
+  dispatch_copy(flat_dtype, dst_dtype, [&](auto s, auto d) {
+    hipLaunchKernelGGL((unpack_kernel<tag_t<decltype(s)>, tag_t<decltype(d)>>), dim3(nblocks), dim3(kMTBlock), 0,
+                       stream, entries, prefix, ntensors, flat, scale);
+  });
 }
 
 // --------------------------------------------------------------------------------------------
@@ -398,39 +357,26 @@ void launch_unpack(const PackEntry* entries, const int32_t* prefix, int ntensors
 // wave butterfly, then the 4 waves through LDS. One plain 8-byte store per block.
 template <typename G>
 __global__ __launch_bounds__(kMTBlock) void sqsum_list_kernel(LarsList list, float* __restrict__ partials) {
-  const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
-  const SgdEntry& e = list.l.e[t];
-  const int64_t chunk0 = (int64_t)(blockIdx.x - list.l.prefix[t]) * kMTChunk;
-  const int64_t end = min(e.numel, chunk0 + (int64_t)kMTChunk);
-  const float* __restrict__ p = e.param;
-  const G* __restrict__ g = reinterpret_cast<const G*>(e.grad);
+  const auto c = find_chunk(list.l.prefix, list.l.ntensors, list.l.e);
+  const float* __restrict__ p = c.e.param;
+  const G* __restrict__ g = reinterpret_cast<const G*>(c.e.grad);
   float sp = 0.f, sg = 0.f;
-  const bool aligned = (((p ? reinterpret_cast<uintptr_t>(p) : 0) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
-  if (aligned && end - chunk0 == kMTChunk) {
+  for_chunk(
+      c, aligned16(p, g),
+      [&](int64_t i) {
+        const float4_t gv = load4_f32(g + i);
+        const float4_t pv = p ? *reinterpret_cast<const float4_t*>(p + i) : float4_t{0, 0, 0, 0};
 #pragma unroll
-    for (int k = 0; k < kMTPerThread / 4; ++k) {
-      const int64_t i = chunk0 + ((int64_t)k * kMTBlock + threadIdx.x) * 4;
-      float4_t gv;
-      if constexpr (sizeof(G) == 4) {
-        gv = *reinterpret_cast<const float4_t*>(reinterpret_cast<const float*>(g) + i);
-      } else {
-        ushort4_t gr = *reinterpret_cast<const ushort4_t*>(reinterpret_cast<const bf16_t*>(g) + i);
-        gv = float4_t{bf16_to_f32(gr.x), bf16_to_f32(gr.y), bf16_to_f32(gr.z), bf16_to_f32(gr.w)};
-      }
-      const float4_t pv = p ? *reinterpret_cast<const float4_t*>(p + i) : float4_t{0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sg = fmaf(gv[j], gv[j], sg);
-        sp = fmaf(pv[j], pv[j], sp);
-      }
-    }
-  } else {
-    for (int64_t i = chunk0 + threadIdx.x; i < end; i += kMTBlock) {
-      const float gv = Cvt<G>::to_f32(g[i]);
-      sg = fmaf(gv, gv, sg);
-      if (p) sp = fmaf(p[i], p[i], sp);
-    }
-  }
+        for (int j = 0; j < 4; ++j) {
+          sg = fmaf(gv[j], gv[j], sg);
+          sp = fmaf(pv[j], pv[j], sp);
+        }
+      },
+      [&](int64_t i) {
+        const float gv = Cvt<G>::to_f32(g[i]);
+        sg = fmaf(gv, gv, sg);
+        if (p) sp = fmaf(p[i], p[i], sp);
+      });
   sp = wave_sum(sp);
   sg = wave_sum(sg);
   __shared__ float sm[2][kMTBlock / kWave];
@@ -524,24 +470,23 @@ __global__ __launch_bounds__(kFinBlock) void lars_finalize_kernel(const LarsTens
 
 template <typename G, bool kEma>
 __device__ __forceinline__ void lars_body(const LarsList& list, const LarsTensor* __restrict__ table,
-                                          const float* __restrict__ ws, int t, float* ema, float omd) {
-  const int row = list.tensor_base + t;
+                                          const float* __restrict__ ws, const Chunk<SgdEntry>& ch, float* ema,
+                                          float omd) {
+  const int row = list.tensor_base + ch.t;
   const float c = ws[0], llr = ws[kLarsHead + row];
   const float wd = table[row].weight_decay, mu = table[row].momentum;
-  update_chunk<G, true, kEma>(list.l.e[t], (int64_t)(blockIdx.x - list.l.prefix[t]) * kMTChunk,
-                              [&](float pv, float gv, float mv, float& po, float& mo) {
-                                float d = gv * c;
-                                if (wd != 0.f) d = fmaf(wd, pv, d);
-                                mo = fmaf(mu, mv, llr * d);
-                                po = pv - mo;
-                              }, ema, omd);
+  update_chunk<G, true, kEma>(ch, [&](float pv, float gv, float mv, float& po, float& mo) {
+    float d = gv * c;
+    if (wd != 0.f) d = fmaf(wd, pv, d);
+    mo = fmaf(mu, mv, llr * d);
+    po = pv - mo;
+  }, ema, omd);
 }
 
 template <typename G>
 __global__ __launch_bounds__(kMTBlock) void lars_list_kernel(LarsList list, const LarsTensor* __restrict__ table,
                                                              const float* __restrict__ ws) {
-  const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
-  lars_body<G, false>(list, table, ws, t, nullptr, 0.f);
+  lars_body<G, false>(list, table, ws, find_chunk(list.l.prefix, list.l.ntensors, list.l.e), nullptr, 0.f);
 }
 
 template <typename G>
@@ -549,17 +494,18 @@ __global__ __launch_bounds__(kMTBlock) void lars_ema_list_kernel(LarsList list, 
                                                                  const float* __restrict__ omd,
                                                                  const LarsTensor* __restrict__ table,
                                                                  const float* __restrict__ ws) {
-  const int t = find_tensor(list.l.prefix, list.l.ntensors, blockIdx.x);
-  lars_body<G, true>(list, table, ws, t, ema.ema[t], omd[0]);
+  const auto c = find_chunk(list.l.prefix, list.l.ntensors, list.l.e);
+  lars_body<G, true>(list, table, ws, c, ema.ema[c.t], omd[0]);
 }
 
 void launch_sqsum_list(const LarsList& list, int nblocks, int grad_dtype, float* ws, int ntensors,
                        hipStream_t stream) {
   if (nblocks <= 0 || list.l.ntensors <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
   float* partials = ws + lars_partials_offset(ntensors);
-  if (grad_dtype == kF32) hipLaunchKernelGGL((sqsum_list_kernel<float>), grid, block, 0, stream, list, partials);
-  else hipLaunchKernelGGL((sqsum_list_kernel<bf16_t>), grid, block, 0, stream, list, partials);
+  dispatch_dtype(grad_dtype, [&](auto g) {
+    hipLaunchKernelGGL((sqsum_list_kernel<tag_t<decltype(g)>>), dim3(nblocks), dim3(kMTBlock), 0, stream, list,
+                       partials);
+  });
 }
 
 void launch_lars_finalize(const LarsTensor* table, int ntensors, const float* lr_dev, float grad_scale,
@@ -572,19 +518,19 @@ void launch_lars_finalize(const LarsTensor* table, int ntensors, const float* lr
 void launch_lars_list(const LarsList& list, int nblocks, int grad_dtype, const LarsTensor* table, const float* ws,
                       hipStream_t stream) {
   if (nblocks <= 0 || list.l.ntensors <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (grad_dtype == kF32) hipLaunchKernelGGL((lars_list_kernel<float>), grid, block, 0, stream, list, table, ws);
-  else hipLaunchKernelGGL((lars_list_kernel<bf16_t>), grid, block, 0, stream, list, table, ws);
+  dispatch_dtype(grad_dtype, [&](auto g) {
+    hipLaunchKernelGGL((lars_list_kernel<tag_t<decltype(g)>>), dim3(nblocks), dim3(kMTBlock), 0, stream, list, table,
+                       ws);
+  });
 }
 
 void launch_lars_ema_list(const LarsList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
                           const LarsTensor* table, const float* ws, hipStream_t stream) {
   if (nblocks <= 0 || list.l.ntensors <= 0) return;
-  dim3 grid(nblocks), block(kMTBlock);
-  if (grad_dtype == kF32)
-    hipLaunchKernelGGL((lars_ema_list_kernel<float>), grid, block, 0, stream, list, ema, omd, table, ws);
-  else
-    hipLaunchKernelGGL((lars_ema_list_kernel<bf16_t>), grid, block, 0, stream, list, ema, omd, table, ws);
+  dispatch_dtype(grad_dtype, [&](auto g) {
+    hipLaunchKernelGGL((lars_ema_list_kernel<tag_t<decltype(g)>>), dim3(nblocks), dim3(kMTBlock), 0, stream, list, ema,
+                       omd, table, ws);
+  });
 }
 
 }  // namespace dla

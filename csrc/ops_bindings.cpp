@@ -139,22 +139,9 @@ static void sgd_step_list_impl(const std::vector<at::Tensor>& params, const std:
   const bool use_m = !moms.empty();
   const SgdParams hp{(float)lr, (float)momentum, (float)dampening, (float)weight_decay, (float)grad_scale,
                      nesterov ? 1 : 0, first_step ? 1 : 0};
-  const int chunk = mt_chunk_elems();
   // every launch is built, and so every tensor checked, before the first one runs: a bad tensor anywhere
   // in the list raises with nothing updated
-  struct Launch {
-    SgdList list;
-    EmaSlots ema;
-    int blocks;
-  };
-  std::vector<Launch> launches;
-  Launch cur{};
-  auto flush = [&]() {
-    if (cur.list.ntensors == 0) return;
-    cur.list.prefix[cur.list.ntensors] = cur.blocks;
-    launches.push_back(cur);
-    cur = Launch{};
-  };
+  ListBatcher<SgdEntry> lists("sgd_step_list");
   if (emas) check_omd(*omd, grads[0], "sgd_step_list");
   for (size_t i = 0; i < params.size(); ++i) {
     const at::Tensor& p = params[i];
@@ -185,16 +172,10 @@ static void sgd_step_list_impl(const std::vector<at::Tensor>& params, const std:
     }
     if (emas) check_ema((*emas)[i], p, i, "sgd_step_list");
     e.numel = p.numel();
-    if (e.numel == 0) continue;
-    cur.list.prefix[cur.list.ntensors] = cur.blocks;
-    if (emas) cur.ema.ema[cur.list.ntensors] = (*emas)[i].data_ptr<float>();
-    cur.list.e[cur.list.ntensors++] = e;
-    cur.blocks += (int)((e.numel + chunk - 1) / chunk);
-    if (cur.list.ntensors == kMaxList) flush();
+    lists.add(e, emas ? (*emas)[i].data_ptr<float>() : nullptr);
   }
-  flush();
   hipStream_t st = current_stream(grads[0]);
-  for (const Launch& L : launches) {
+  for (const auto& L : lists.finish()) {
     if (emas) launch_sgd_ema_list(L.list, L.ema, omd->data_ptr<float>(), L.blocks, gdt, use_m, hp, st);
     else launch_sgd_list(L.list, L.blocks, gdt, use_m, hp, st);
   }
@@ -224,19 +205,7 @@ static void ema_list_op(const char* op, const std::vector<at::Tensor>& targets, 
   TORCH_CHECK(shadows.empty() || shadows.size() == targets.size(), op, ": shadow list size mismatch");
   if (targets.empty()) return;
   if (omd) check_omd(*omd, targets[0], op);
-  const int chunk = mt_chunk_elems();
-  struct Launch {
-    EmaList list;
-    int blocks;
-  };
-  std::vector<Launch> launches;
-  Launch cur{};
-  auto flush = [&]() {
-    if (cur.list.ntensors == 0) return;
-    cur.list.prefix[cur.list.ntensors] = cur.blocks;
-    launches.push_back(cur);
-    cur = Launch{};
-  };
+  ListBatcher<EmaEntry> lists(op);
   for (size_t i = 0; i < targets.size(); ++i) {
     const at::Tensor& x = targets[i];
     check_dev(x, "target");
@@ -255,16 +224,10 @@ static void ema_list_op(const char* op, const std::vector<at::Tensor>& targets, 
       e.shadow = reinterpret_cast<uint16_t*>(s.data_ptr());
     }
     e.numel = x.numel();
-    if (e.numel == 0) continue;
-    TORCH_CHECK(cur.blocks + (e.numel + chunk - 1) / chunk < ((int64_t)1 << 30), op, ": too many chunks");
-    cur.list.prefix[cur.list.ntensors] = cur.blocks;
-    cur.list.e[cur.list.ntensors++] = e;
-    cur.blocks += (int)((e.numel + chunk - 1) / chunk);
-    if (cur.list.ntensors == kMaxList) flush();
+    lists.add(e);
   }
-  flush();
   hipStream_t st = current_stream(targets[0]);
-  for (const Launch& L : launches) {
+  for (const auto& L : lists.finish()) {
     if (omd) launch_ema_update_list(L.list, L.blocks, omd->data_ptr<float>(), st);
     else launch_ema_swap_list(L.list, L.blocks, st);
   }
@@ -348,36 +311,17 @@ class LarsPlan {
     TORCH_CHECK(!update || (params.size() == T && moms.size() == T && lr_dev_.defined()),
                 "lars: the update needs a parameter and a momentum buffer per gradient, and lr_dev");
     TORCH_CHECK(shadows.empty() || shadows.size() == T, "lars: shadow list size mismatch");
-    const int chunk = mt_chunk_elems();
-    // the launches of both passes, built once: by-value lists split at kMaxList tensors and at grad dtype changes
-    struct Launch {
-      LarsList list;
-      EmaSlots ema;
-      int blocks, gdt;
-    };
-    std::vector<Launch> launches;
-    Launch cur{};
-    int block_base = 0;
-    auto flush = [&](int next_row) {
-      if (cur.list.l.ntensors > 0) {
-        cur.list.l.prefix[cur.list.l.ntensors] = cur.blocks;
-        launches.push_back(cur);
-        block_base += cur.blocks;
-      }
-      cur = Launch{};
-      cur.list.tensor_base = next_row;
-      cur.list.block_base = block_base;
-    };
-    flush(0);
+    // the launches of both passes, built once: by-value lists split at kMaxList tensors and at grad dtype changes;
+    // empty tensors keep their slot, so that slot t of a launch is table row tensor_base + t
+    ListBatcher<SgdEntry> lists("lars", /*keep_empty=*/true);
     for (size_t i = 0; i < T; ++i) {
       const at::Tensor& g = grads[i];
       check_dev(g, "grad");
       TORCH_CHECK(g.device() == ws_.device(), "lars: tensor ", i, " is on another device than the plan");
       TORCH_CHECK(g.numel() == numels_[i], "lars: tensor ", i, " has ", g.numel(), " elements, the plan ", numels_[i]);
-      const int gdt = dtype_code(g);
-      if (cur.list.l.ntensors > 0 && gdt != cur.gdt) flush((int)i);
-      cur.gdt = gdt;
+      lists.tag(dtype_code(g));
       SgdEntry e{};
+      float* ema = nullptr;
       e.grad = g.data_ptr();
       e.numel = g.numel();
       if (!params.empty()) {
@@ -403,24 +347,23 @@ class LarsPlan {
         }
         if (emas) {
           check_ema((*emas)[i], params[i], i, "lars");
-          cur.ema.ema[cur.list.l.ntensors] = (*emas)[i].data_ptr<float>();
+          ema = (*emas)[i].data_ptr<float>();
         }
       }
-      cur.list.l.prefix[cur.list.l.ntensors] = cur.blocks;
-      cur.list.l.e[cur.list.l.ntensors++] = e;
-      cur.blocks += (int)((e.numel + chunk - 1) / chunk);
-      if (cur.list.l.ntensors == kMaxList) flush((int)i + 1);
+      lists.add(e, ema);
     }
-    flush((int)T);
-    TORCH_CHECK(block_base == nblocks_, "lars: chunk count changed since the plan was built");
+    const auto& launches = lists.finish();
+    TORCH_CHECK(lists.total_blocks() == nblocks_, "lars: chunk count changed since the plan was built");
     hipStream_t st = current_stream(ws_);
-    for (const Launch& L : launches) launch_sqsum_list(L.list, L.blocks, L.gdt, ws(), (int)T, st);
+    for (const auto& L : launches)
+      launch_sqsum_list({L.list, L.tensor_base, L.block_base}, L.blocks, L.tag, ws(), (int)T, st);
     launch_lars_finalize(table(), (int)T, lr_dev_.defined() ? lr_dev_.data_ptr<float>() : nullptr, (float)grad_scale,
                          (float)max_grad_norm, ws(), st);
     if (update)
-      for (const Launch& L : launches) {
-        if (emas) launch_lars_ema_list(L.list, L.ema, omd->data_ptr<float>(), L.blocks, L.gdt, table(), ws(), st);
-        else launch_lars_list(L.list, L.blocks, L.gdt, table(), ws(), st);
+      for (const auto& L : launches) {
+        const LarsList list{L.list, L.tensor_base, L.block_base};
+        if (emas) launch_lars_ema_list(list, L.ema, omd->data_ptr<float>(), L.blocks, L.tag, table(), ws(), st);
+        else launch_lars_list(list, L.blocks, L.tag, table(), ws(), st);
       }
     launches_ = (int)launches.size() * (update ? 2 : 1) + 1;
   }
@@ -465,34 +408,15 @@ void pack_tensors_on(const std::vector<at::Tensor>& ts, const std::vector<int64_
                      float scale, hipStream_t st) {
   TORCH_CHECK(ts.size() == offs.size(), "pack: tensors/offsets size mismatch");
   const int fdt = dtype_code(flat);
-  const int chunk = mt_chunk_elems();
   // as in sgd_step_list: all launches built and checked first, so a bad slot leaves `flat` untouched
-  struct Launch {
-    PackList list;
-    int blocks, sdt;
-  };
-  std::vector<Launch> launches;
-  Launch cur{};
-  auto flush = [&]() {
-    if (cur.list.ntensors == 0) return;
-    cur.list.prefix[cur.list.ntensors] = cur.blocks;
-    launches.push_back(cur);
-    cur = Launch{};
-  };
+  ListBatcher<PackEntry> lists("pack");
   for (size_t i = 0; i < ts.size(); ++i) {
     check_dev(ts[i], "pack tensor");
-    const int d = dtype_code(ts[i]);
-    if (cur.list.ntensors > 0 && d != cur.sdt) flush();
-    cur.sdt = d;
+    lists.tag(dtype_code(ts[i]));  // a launch has one source dtype
     TORCH_CHECK(offs[i] >= 0 && offs[i] + ts[i].numel() <= flat.numel(), "pack: slot ", i, " out of range");
-    if (ts[i].numel() == 0) continue;
-    cur.list.prefix[cur.list.ntensors] = cur.blocks;
-    cur.list.e[cur.list.ntensors++] = PackEntry{ts[i].data_ptr(), ts[i].numel(), offs[i]};
-    cur.blocks += (int)((ts[i].numel() + chunk - 1) / chunk);
-    if (cur.list.ntensors == kMaxList) flush();
+    lists.add(PackEntry{ts[i].data_ptr(), ts[i].numel(), offs[i]});
   }
-  flush();
-  for (const Launch& L : launches) launch_pack_list(L.list, L.blocks, L.sdt, fdt, flat.data_ptr(), scale, st);
+  for (const auto& L : lists.finish()) launch_pack_list(L.list, L.blocks, L.tag, fdt, flat.data_ptr(), scale, st);
 }
 
 void pack_list(std::vector<at::Tensor> ts, std::vector<int64_t> offs, at::Tensor flat, double scale) {
@@ -674,17 +598,25 @@ std::vector<at::Tensor> xent_metrics_fwd(at::Tensor logits, at::Tensor target, d
   return {stats, ws};
 }
 
+// The forward's outputs as the backward wrappers get them back: nstats statistics, nstats / 2 + 2 workspace
+// floats per row and the mean. Returns gout as a contiguous fp32 tensor.
+static at::Tensor check_xent_bwd_args(const at::Tensor& ws, const at::Tensor& stats, const at::Tensor& gout, int B,
+                                      int nstats, const char* op) {
+  check_dev(ws, "ws");
+  check_dev(stats, "stats");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == (nstats / 2 + 2) * (int64_t)B + 1, op,
+              ": bad workspace");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == nstats, op, ": bad stats");
+  TORCH_CHECK(gout.is_cuda() && gout.numel() == 1, op, ": gout must be one value on the GPU");
+  return gout.to(at::kFloat).contiguous();
+}
+
 at::Tensor xent_smooth_bwd(at::Tensor logits, at::Tensor target, at::Tensor ws, at::Tensor stats, at::Tensor gout,
                            double eps) {
   check_xent_args(logits, target, eps, "xent_smooth_bwd");
   const int B = (int)logits.size(0), C = (int)logits.size(1);
-  check_dev(ws, "ws");
-  check_dev(stats, "stats");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 4 * (int64_t)B + 1, "xent_smooth_bwd: bad workspace");
-  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == 4, "xent_smooth_bwd: bad stats");
-  TORCH_CHECK(gout.is_cuda() && gout.numel() == 1, "xent_smooth_bwd: gout must be one value on the GPU");
+  auto g = check_xent_bwd_args(ws, stats, gout, B, 4, "xent_smooth_bwd");
   auto d = at::empty_like(logits);
-  auto g = gout.to(at::kFloat).contiguous();
   launch_xent_smooth_bwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), stats.data_ptr<float>(),
                          g.data_ptr<float>(), d.data_ptr(), B, C, (float)eps, dtype_code(logits),
                          current_stream(logits));
@@ -718,13 +650,8 @@ at::Tensor xent_mix_bwd(at::Tensor logits, at::Tensor target_a, at::Tensor targe
                         at::Tensor stats, at::Tensor gout, double eps) {
   check_xent_mix_args(logits, target_a, target_b, lam, eps, "xent_mix_bwd");
   const int B = (int)logits.size(0), C = (int)logits.size(1);
-  check_dev(ws, "ws");
-  check_dev(stats, "stats");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 3 * (int64_t)B + 1, "xent_mix_bwd: bad workspace");
-  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == 2, "xent_mix_bwd: bad stats");
-  TORCH_CHECK(gout.is_cuda() && gout.numel() == 1, "xent_mix_bwd: gout must be one value on the GPU");
+  auto g = check_xent_bwd_args(ws, stats, gout, B, 2, "xent_mix_bwd");
   auto d = at::empty_like(logits);
-  auto g = gout.to(at::kFloat).contiguous();
   launch_xent_mix_bwd(logits.data_ptr(), target_a.data_ptr<int64_t>(), target_b.data_ptr<int64_t>(),
                       lam.data_ptr<float>(), ws.data_ptr<float>(), stats.data_ptr<float>(), g.data_ptr<float>(),
                       d.data_ptr(), B, C, (float)eps, dtype_code(logits), current_stream(logits));

@@ -175,11 +175,12 @@ SANITIZE_DIR = ROOT / "build" / "sanitize"
 def sanitize_check(run: bool = True) -> int:
     """CPU AddressSanitizer + UndefinedBehaviorSanitizer builds of the host C++ that needs no GPU: the comm engine
     (plan builder, virtual-rank host executor, IPC host protocol; csrc/tests/host_check.cpp) and the environment
-    switch type (csrc/include/dla_knob.h; csrc/tests/knob_check.cpp) -- the GPU pool runs no sanitizers, so this
+    switch type (csrc/include/dla_knob.h; csrc/tests/knob_check.cpp) and the tensor-list batcher
+    (csrc/include/dla_lists.h; csrc/tests/list_check.cpp) -- the GPU pool runs no sanitizers, so this
     is where they apply. Returns the first non-zero exit status of the checks (0 = all clean)."""
     SANITIZE_DIR.mkdir(parents=True, exist_ok=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    for name, extra in (("host_check", [CSRC / "comm" / "plan.cpp"]), ("knob_check", [])):
+    for name, extra in (("host_check", [CSRC / "comm" / "plan.cpp"]), ("knob_check", []), ("list_check", [])):
         exe = SANITIZE_DIR / name
         cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                "-fno-omit-frame-pointer", "-pthread", str(CSRC / "tests" / f"{name}.cpp"), *map(str, extra), "-o", str(exe)]

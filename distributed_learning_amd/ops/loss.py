@@ -66,17 +66,23 @@ def _check_smoothing(label_smoothing: float) -> float:
     return eps
 
 
+def _row_loss(x: torch.Tensor, xt: torch.Tensor, valid: torch.Tensor, eps: float) -> torch.Tensor:
+    """Row losses ``lse - (1 - eps) * xt - eps * mean(x)`` of both fallbacks, 0 for an invalid row; ``eps == 0``
+    leaves the mean out, as the kernels do."""
+    row = torch.logsumexp(x, dim=1) - (1.0 - eps) * xt
+    if eps > 0:
+        row = row - (eps / x.shape[1]) * x.sum(dim=1)
+    return torch.where(valid, row, torch.zeros_like(row))
+
+
 def _metrics_fallback(logits: torch.Tensor, target: torch.Tensor, eps: float, k: int):
     """The kernels' semantics in plain torch (CPU tensors, unsupported dtypes, no extension)."""
     x = logits if logits.dtype == torch.float64 else logits.float()
-    B, C = x.shape
+    C = x.shape[1]
     valid = (target >= 0) & (target < C)
     t = torch.where(valid, target, torch.zeros_like(target))
     xt = x.gather(1, t[:, None]).squeeze(1)
-    row = torch.logsumexp(x, dim=1) - (1.0 - eps) * xt
-    if eps > 0:
-        row = row - (eps / C) * x.sum(dim=1)
-    row = torch.where(valid, row, torch.zeros_like(row))
+    row = _row_loss(x, xt, valid, eps)
     xd, xtd = x.detach(), xt.detach()[:, None]
     cols = torch.arange(C, device=x.device)[None, :]
     rank = ((xd > xtd) | ((xd == xtd) & (cols < t[:, None]))).sum(dim=1)
@@ -139,10 +145,7 @@ def _mix_fallback(logits: torch.Tensor, target_a: torch.Tensor, target_b: torch.
     # a term whose weight is exactly 0 is left out: a -inf logit there adds nothing
     xt = torch.where(wa != 0, wa * x.gather(1, ta[:, None]).squeeze(1), zero) \
         + torch.where(wb != 0, wb * x.gather(1, tb[:, None]).squeeze(1), zero)
-    row = torch.logsumexp(x, dim=1) - (1.0 - eps) * xt
-    if eps > 0:
-        row = row - (eps / C) * x.sum(dim=1)
-    row = torch.where(valid, row, torch.zeros_like(row))
+    row = _row_loss(x, xt, valid, eps)
     return row.sum() / valid.sum().to(row.dtype)
 
 

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import dist_util
+import list_shapes
 from ema_oracle import EXACT_DECAYS, GENERAL_DECAYS, bound_violations, check_step, ema_oracle_step, omd32, replay32
 from test_gpu_lars import _tensors as lars_tensors
 from test_gpu_sgd import ROWS, _cycle, _grads, _like, _tensors, sgd_oracle_step
@@ -129,28 +130,36 @@ def test_lars(cuda, dtype, max_grad_norm):
             _close(on.state[p]["ema"], e64)
 
 
-@pytest.mark.parametrize("count", [33, 70])
+@pytest.mark.parametrize("count", [33, 70, "edges"])
 @pytest.mark.parametrize("name", ["sgd", "lars"])
 def test_list_boundary_and_subset_without_gradient(cuda, name, count):
+    """33 and 70 tensors against 32 per launch; "edges": the list of tests/list_shapes.py, whose zero-element tensor
+    FusedSGD hands to the binding and FusedLARS leaves out (so there it never has a gradient, nor an EMA)."""
     from distributed_learning_amd.ops.optim import FusedLARS, FusedSGD
 
+    edges = count == "edges"
+    count = list_shapes.COUNT if edges else count
+    never = {list_shapes.EMPTY} if edges and name == "lars" else set()
     cls, kw = {"sgd": (FusedSGD, dict(lr=0.05, momentum=0.9, weight_decay=1e-4)),
                "lars": (FusedLARS, dict(lr=0.3, weight_decay=1e-4))}[name]
     decay = EXACT_DECAYS[1]
     omd = omd32(decay)
-    make = lambda: [p.requires_grad_() for p in _cycle(cuda, torch.bfloat16, count, torch.Generator().manual_seed(count))]
+    tensors = lambda gen: list_shapes.edge_list(cuda, torch.bfloat16, gen) if edges else _cycle(cuda, torch.bfloat16, count, gen)
+    make = lambda: [p.requires_grad_() for p in tensors(torch.Generator().manual_seed(count))]
     ps_on, ps_off = make(), make()
     on, off = cls(ps_on, master_weights=True, ema_decay=decay, **kw), cls(ps_off, master_weights=True, **kw)
     gen = torch.Generator().manual_seed(3)
     idle = {1, count // 2, 31, 32, count - 1}
     for step in range(3):
         grads = _grads(ps_on, gen, mult=lambda t: (t + 1.0) / 64)
-        if step == 1:
-            grads = [None if t in idle else g for t, g in enumerate(grads)]
+        grads = [None if t in never or (step == 1 and t in idle) else g for t, g in enumerate(grads)]
         before, after = _step_pair(on, off, ps_on, ps_off, grads, omd, True)
         if step == 1:  # said once more, outside check_step: not a bit of an idle tensor's EMA moves
             assert all(torch.equal(before[t][1], after[t][1]) for t in idle)
-            assert not any(torch.equal(before[t][1], after[t][1]) for t in range(count) if t not in idle)
+            # ("edges": but for the empty tensor and the one-element ones, whose single omd * (p_new - e) may
+            # round to no change)
+            moving = [t for t in range(count) if t not in idle and (ps_on[t].numel() > 1 or not edges)]
+            assert [t for t in moving if torch.equal(before[t][1], after[t][1])] == []
 
 
 def test_misaligned_ema_takes_the_scalar_path_to_the_same_values(cuda):
@@ -253,28 +262,41 @@ def test_graph_capture_follows_the_decay_schedule(cuda, name):
 
 
 def test_ema_update_list(cuda):
-    """Buffer-sized tensors, 40 of them (two launches): the replay criteria for every decay."""
+    """Buffer-sized tensors, 40 of them (two launches): the replay criteria for every decay. Then the same on the
+    list of tests/list_shapes.py, and that list's exchange by ema_swap_list, bit for bit, and back."""
     from distributed_learning_amd.ops import _ext
 
     C = _ext.require()
     gen = torch.Generator().manual_seed(6)
     sizes = [(1, 64, 2048)[t % 3] for t in range(40)]
-    for decay in DECAYS:
-        omd = omd32(decay)
-        omd_dev = torch.full((1,), 1.0 - decay, dtype=torch.float32, device=cuda)
-        assert float(omd_dev) == omd
-        emas = [torch.randn(n, generator=gen).to(cuda) for n in sizes]
-        for _ in range(2):
-            xs = [torch.randn(n, generator=gen).to(cuda) for n in sizes]
-            old = [e.clone() for e in emas]
-            keep = [x.clone() for x in xs]
-            C.ema_update_list(emas, xs, omd_dev)
-            assert all(torch.equal(a, b) for a, b in zip(xs, keep))  # the sources are read only
-            for e, o, x in zip(emas, old, xs):
-                if decay in EXACT_DECAYS:
-                    assert torch.equal(e, replay32(o, x, omd))
-                assert bound_violations(e, o, x, omd) == 0
+    for make in (lambda: [torch.randn(n, generator=gen).to(cuda) for n in sizes],
+                 lambda: list_shapes.edge_list(cuda, torch.float32, gen)):
+        for decay in DECAYS:
+            omd = omd32(decay)
+            omd_dev = torch.full((1,), 1.0 - decay, dtype=torch.float32, device=cuda)
+            assert float(omd_dev) == omd
+            emas = make()
+            for _ in range(2):
+                xs = make()
+                old = [e.clone() for e in emas]
+                keep = [x.clone() for x in xs]
+                C.ema_update_list(emas, xs, omd_dev)
+                assert all(torch.equal(a, b) for a, b in zip(xs, keep))  # the sources are read only
+                for e, o, x in zip(emas, old, xs):
+                    if decay in EXACT_DECAYS:
+                        assert torch.equal(e, replay32(o, x, omd))
+                    assert bound_violations(e, o, x, omd) == 0
     C.ema_update_list([], [], omd_dev)  # an empty list is no launch
+    # the exchange, on inputs of its own: the list of list_shapes.py, a bf16 shadow for every other tensor
+    xs, emas = list_shapes.edge_list(cuda, torch.float32, gen), list_shapes.edge_list(cuda, torch.float32, gen)
+    assert len(xs) == list_shapes.COUNT and xs[list_shapes.EMPTY].numel() == 0
+    x0, e0 = [x.clone() for x in xs], [e.clone() for e in emas]
+    shadows = [torch.empty_like(x, dtype=torch.bfloat16) if t % 2 else None for t, x in enumerate(xs)]
+    C.ema_swap_list(xs, emas, shadows)
+    assert all(torch.equal(x, e) for x, e in zip(xs, e0)) and all(torch.equal(e, x) for e, x in zip(emas, x0))
+    assert all(s is None or torch.equal(s, x.to(torch.bfloat16)) for s, x in zip(shadows, xs))
+    C.ema_swap_list(xs, emas, shadows)
+    assert all(torch.equal(x, b) for x, b in zip(xs, x0)) and all(torch.equal(e, b) for e, b in zip(emas, e0))
 
 
 def _bn_conv_model(cuda):

@@ -14,6 +14,7 @@ import math
 import pytest
 import torch
 
+import list_shapes
 from test_lars import ATOL, RTOL, hyper, lars_oracle_step
 
 pytestmark = pytest.mark.gpu
@@ -53,6 +54,13 @@ def test_l2norm_matches_float64(cuda, dtype):
     b = ops.multi_tensor_l2norm(mixed)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     _close(a[0], torch.stack([t.double().cpu().norm() for t in mixed]))
+    # the list of tests/list_shapes.py: three launches, the zero-element tensor keeps its slot (and its row)
+    edges = list_shapes.edge_list(cuda, list_shapes.mixed_dtypes(), torch.Generator().manual_seed(3), two_d=True)
+    per, total = ops.multi_tensor_l2norm(edges)
+    ref = torch.stack([t.double().cpu().norm() for t in edges])
+    _close(per, ref)
+    _close(total, ref.norm().reshape(1))
+    assert float(per[list_shapes.EMPTY]) == 0.0
 
 
 class Pair:
@@ -115,29 +123,65 @@ def test_update_matches_oracle(cuda, dtype):
     assert pair.opt.last_launches == 3  # one square-sum launch, the finalize, one update launch
 
 
-@pytest.mark.parametrize("count", [33, 70])
+@pytest.mark.parametrize("count", [33, 70, "edges"])
 def test_list_boundary_and_subset(cuda, count):
+    """33 and 70 fp32 tensors against 32 per launch; "edges": the list of tests/list_shapes.py, fp32 tensors and
+    then bf16 ones with masters (FusedLARS itself leaves the zero-element tensor out, and it has no trust)."""
+    edges = count == "edges"
+    count = list_shapes.COUNT if edges else count
     g = torch.Generator().manual_seed(count)
-    ps = [torch.randn(1, (5, 4096, 5000)[t % 3], generator=g).to(cuda) for t in range(count)]
+    if edges:
+        ps = list_shapes.edge_list(cuda, list_shapes.mixed_dtypes(), g, two_d=True)
+    else:
+        ps = [torch.randn(1, (5, 4096, 5000)[t % 3], generator=g).to(cuda) for t in range(count)]
     half = count // 2
+    only = set(range(count)) - {list_shapes.EMPTY} if edges else None  # FusedLARS keeps no state for it
     pair = Pair(ps, [(range(0, half), dict(lr=0.4, weight_decay=1e-4)), (range(half, count), dict(lr=0.1, weight_decay=1e-3))],
-                lr=0.1, momentum=0.9, eta=0.02, grad_scale=0.5)
+                lr=0.1, momentum=0.9, eta=0.02, grad_scale=0.5, master_weights=edges)
     _, gnorms, trusts = pair.step(_grads(pair.params, g, mult=lambda t: t + 1.0))
     assert len({round(math.log(t), 3) for t in trusts}) > count // 2  # every slot matters
-    pair.check()
-    assert pair.opt.last_launches == 2 * math.ceil(count / 32) + 1
+    pair.check(only)
+    # square-sum and update launches: one per 32 tensors; "edges": 20 fp32 tensors, then 19 bf16 ones
+    assert pair.opt.last_launches == 2 * (2 if edges else math.ceil(count / 32)) + 1
     # the same optimizer, three tensors with gradients and the rest without: nothing stale may be read
     subset = {1, half, count - 1}
     grads = [g_ if t in subset else None for t, g_ in enumerate(_grads(pair.params, g, mult=lambda t: 3.0 * (t + 1)))]
     before = [p.detach().clone() for p in pair.params]
     G, _, _ = pair.step(grads)
     _close(pair.opt.last_grad_norm, torch.tensor([G]))
-    pair.check()
+    pair.check(only)
     for t, (p, b) in enumerate(zip(pair.params, before)):
         assert torch.equal(p.detach(), b) == (t not in subset)
-    assert pair.opt.last_launches == 3
+    assert pair.opt.last_launches == (5 if edges else 3)  # "edges": the subset has both dtypes
     pair.step(_grads(pair.params, g, mult=lambda t: t + 1.0))  # and back to the whole list
-    pair.check()
+    pair.check(only)
+    if edges:
+        _direct_update_keeps_the_empty_slot(cuda, g)
+
+
+def _direct_update_keeps_the_empty_slot(cuda, g):
+    """lars_step_list called as FusedLARS calls it, but with the zero-element tensor left in: its slot takes a table
+    row and no block in the square-sum and in the update launches, and every other tensor steps as the oracle does."""
+    from distributed_learning_amd.ops import _ext
+
+    C = _ext.require()
+    n = list_shapes.COUNT
+    ps = list_shapes.edge_list(cuda, torch.float32, g, two_d=True)  # fp32 masters; gradients fp32, then bf16
+    grads = [_like(p, torch.randn(p.shape, generator=g) * (t + 1.0)).to(dt)
+             for t, (p, dt) in enumerate(zip(ps, list_shapes.mixed_dtypes()))]
+    moms = [torch.zeros_like(p) for p in ps]
+    hp = [dict(lr=0.2, momentum=0.9, weight_decay=1e-4, eta=0.02, eps=0.0, adapt=True)] * n
+    plan = C.LarsPlan([p.numel() for p in ps], [0] * n, [True] * n, [1e-4] * n, [0.02] * n, [0.0] * n, [0.9] * n,
+                      torch.full((1,), 0.2, device=cuda), ps[0])
+    P, M = [p.double().cpu().clone() for p in ps], [torch.zeros_like(p).double().cpu() for p in ps]
+    for _ in range(2):
+        C.lars_step_list(plan, ps, grads, moms, [], 0.5, 1.0)
+        G, _, _ = lars_oracle_step(P, M, grads, hp, 0.5, 1.0)
+        _close(plan.grad_norm(), torch.tensor([G]))
+        for p, m, ref, mref in zip(ps, moms, P, M):
+            _close(p, ref)
+            _close(m, mref)
+    assert plan.last_launches() == 2 * 2 + 1 and ps[list_shapes.EMPTY].numel() == 0
 
 
 def test_plan_cache_is_bounded(cuda):

@@ -15,6 +15,8 @@ import functools
 import pytest
 import torch
 
+import list_shapes
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float32, torch.bfloat16]
@@ -134,16 +136,20 @@ def _cycle(dev, dtypes, count, gen, empty=()):
 
 
 @pytest.mark.parametrize("flat_dtype", DTYPES)
-@pytest.mark.parametrize("count,layout", [(33, "fp32"), (70, "bf16"), (70, "runs"), (40, "empties")])
+@pytest.mark.parametrize("count,layout", [(33, "fp32"), (70, "bf16"), (70, "runs"), (40, "empties"), (40, "edges")])
 def test_pack_list_splits(cuda, count, layout, flat_dtype):
-    """More than 32 tensors per list, a dtype that changes twice along the list, zero-element tensors."""
+    """More than 32 tensors per list, a dtype that changes twice along the list, zero-element tensors; "edges":
+    the list of tests/list_shapes.py."""
     C = _C()
     gen = torch.Generator().manual_seed(count)
     f, b = torch.float32, torch.bfloat16
     dtypes = {"fp32": [f] * count, "bf16": [b] * count, "runs": [f] * 20 + [b] * 35 + [f] * 15,
-              "empties": [f] * 10 + [b] * 30}[layout]
+              "empties": [f] * 10 + [b] * 30, "edges": list_shapes.mixed_dtypes()}[layout]
     empty = (3, 17, 18, 31, 32) if layout == "empties" else ()
-    ts = _cycle(cuda, dtypes, count, gen, empty)
+    if layout == "edges":
+        ts = list_shapes.edge_list(cuda, dtypes, gen)
+    else:
+        ts = _cycle(cuda, dtypes, count, gen, empty)
     offs, total = _offsets(ts, odd=False)
     flat = torch.full((total,), SENTINEL, device=cuda, dtype=flat_dtype)
     C.pack_list(ts, offs, flat, 1.0 / 3.0)

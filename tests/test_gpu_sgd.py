@@ -16,6 +16,7 @@ address (scalar path at full chunk size), and lists of 33 and 70 tensors against
 import pytest
 import torch
 
+import list_shapes
 from test_lars import ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
@@ -159,12 +160,13 @@ def test_mixed_model_steps_both_partitions(cuda):
     assert {("master" in pair.opt.state[p]) for p in pair.params} == {True, False}
 
 
-@pytest.mark.parametrize("count", [33, 70])
+@pytest.mark.parametrize("count", [33, 70, "edges"])
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_list_boundary(cuda, dtype, count):
-    gen = torch.Generator().manual_seed(count)
-    pair = Pair(_cycle(cuda, dtype, count, gen), lr=0.05, momentum=0.9, weight_decay=1e-4,
-                master_weights=dtype != torch.float32)
+    """33 and 70 tensors against 32 per launch; "edges": the list of tests/list_shapes.py."""
+    gen = torch.Generator().manual_seed(list_shapes.COUNT if count == "edges" else count)
+    ps = list_shapes.edge_list(cuda, dtype, gen) if count == "edges" else _cycle(cuda, dtype, count, gen)
+    pair = Pair(ps, lr=0.05, momentum=0.9, weight_decay=1e-4, master_weights=dtype != torch.float32)
     for _ in range(3):
         # scaled by the slot, so every slot matters: randn * (t + 1) / 64. (Unit-variance gradients times t + 1
         # make momentum values of several hundred, whose fp32 rounding alone exceeds ATOL on the elements
