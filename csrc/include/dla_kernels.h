@@ -378,6 +378,7 @@ void set_gemm_persist(int blocks_per_cu);
 // fp32 convolutions on v_mfma_f32_16x16x4_f32 (conv_f32.hip): x NHWC [N][H][W][C], w OHWI [Cout][R][S][C], y NHWC
 // [N][OH][OW][Cout]; C % 4 == 0, Cout % 4 == 0, N * OH * OW < 2^24. accumulate: y += conv instead of y = conv.
 bool conv_f32_supported(int C, int Cout, int64_t M, int K);
+bool conv_f32_divisors_ok(int OH, int OW, int C, int S);
 void set_conv_f32_buffers(int nb);  // 1 or 2 (default) LDS buffers of the fp32 GEMM main loop (A/B)
 // ldx: elements between consecutive pixels of x (C, or more when x is a channel slice of a wider NHWC tensor)
 void launch_conv_f32_fwd(const float* x, int64_t ldx, int N, int H, int W, int C, const float* w, int Cout, int R,
@@ -485,6 +486,8 @@ void launch_stem_wgrad_bn(const void* dy_pool, const uint8_t* pos, const void* x
 // Halo-tiled 64 -> 64 channel 3x3 / stride-1 weight gradient (conv_halo_wgrad.hip): persistent blocks over
 // a padded pixel space, x rows through an LDS ring; splits = partial slabs of [64][9][64] fp32.
 bool halo_wgrad_eligible(int Cin, int Cout, int W, int stride);
+// eligible, and inside the index ranges of the kernel's padded-position decode (what conv3x3_wgrad asks)
+bool halo_wgrad_serves(int N, int H, int W, int Cin, int Cout, int stride);
 void set_halo_wgrad(int mode);  // -1 environment (DLA_HALO_WGRAD, default on), 0 off, 1 on
 int halo_wgrad_splits(int N, int H, int W);
 void launch_conv3x3_halo_wgrad(const void* dy, const void* x, float* partial, int splits, void* dw, int out_dtype,

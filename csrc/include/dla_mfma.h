@@ -27,7 +27,10 @@ typedef short s16x4_t __attribute__((ext_vector_type(4)));
 // m = ceil(2^40 / d), m d = 2^40 + r and 0 <= r < d, so n m / 2^40 = n / d + n r / (d 2^40): the overshoot is below
 // n / 2^40 < 2^-16, and it must stay below 1 / d (the distance of n / d from the next integer), which it does only
 // while d <= 2^16. Past it the quotient can come out one too large (d = 1048577, n = d - 1 gives 1, not 0); a caller
-// that cannot bound its divisors divides in hardware instead (pool.hip pool_fast_index, conv_halo.hip).
+// that cannot bound its divisors divides in hardware instead (pool.hip pool_fast_index, conv_halo.hip). What the proof
+// needs is n d <= 2^40, and the 32-bit sum below holds n m / 2^32 only while n < 2^24 d: a small divisor takes
+// dividends past 2^24 (conv_halo_wgrad.hip: d = W + 2 <= 63, n < 2^24 d by its host gate). Every call site, its
+// bounds and the host check behind each: profiles/index_edges/README.md; emulated in tests/test_index_domain.py.
 struct FastDiv {
   uint32_t d, m_lo, m_hi;
 };

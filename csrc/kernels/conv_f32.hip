@@ -380,6 +380,11 @@ bool conv_f32_supported(int C, int Cout, int64_t M, int K) {
   return C % 4 == 0 && Cout % 4 == 0 && M > 0 && M < (int64_t(1) << 24) && K < (1 << 24);
 }
 
+// the divisors of pixel_of (OW, OH) and of the k -> (tap, c) -> (r, s) decode (C, S): mm::fdiv needs each below 2^16
+bool conv_f32_divisors_ok(int OH, int OW, int C, int S) {
+  return OH < (1 << 16) && OW < (1 << 16) && C < (1 << 16) && S < (1 << 16);
+}
+
 void launch_conv_f32_fwd(const float* x, int64_t ldx, int N, int H, int W, int C, const float* w, int Cout, int R,
                          int S, int pad, int stride, float* y, bool accumulate, hipStream_t st) {
   const ConvGeomF g = make_geom(x, ldx, N, H, W, C, R, S, pad, stride);

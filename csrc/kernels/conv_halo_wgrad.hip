@@ -214,6 +214,14 @@ bool halo_wgrad_eligible(int Cin, int Cout, int W, int stride) {
   return k_halo_wgrad.on() && Cin == kWC && Cout == kWC && stride == 1 && W >= 1 && 2 * (W + 2) + 2 + 3 * kWS <= kWRing;
 }
 
+// The kernel decodes padded positions: q / (W + 2) with q < N (H + 2) (W + 2) and W + 2 <= 63, exact while
+// q < 2^24 (W + 2) (past it mm::fdiv's 32-bit sum wraps), then r / (H + 2) with r < N (H + 2), which needs both
+// mm::fdiv bounds. N (H + 2) < 2^24 serves both divisions. Anything else runs on the implicit-GEMM weight gradient.
+bool halo_wgrad_serves(int N, int H, int W, int Cin, int Cout, int stride) {
+  return halo_wgrad_eligible(Cin, Cout, W, stride) && N >= 0 && H >= 0 &&
+         (int64_t)N * (H + 2) * (W + 2) < (1 << 30) && (int64_t)N * (H + 2) < (1 << 24) && H + 2 < 65536;
+}
+
 static int halo_wgrad_grid(int64_t Q) {
   static const int cus = [] {
     int dev = 0, n = 0;

@@ -574,6 +574,7 @@ bool launch_stem_stream(const void* xs, const void* wpk, void* y, int N, int BH,
   const int64_t P = (int64_t)N * BH * BW;
   const StreamPlan p = stream_geometry(P, 64, false, false);
   if (!stats || stem_stream_rows(P, 64) != p.mg || !p.mg) return false;
+  if (BH >= (1 << 16) || BW >= (1 << 16)) return false;  // sfW / sfH: mm::fdiv needs a divisor below 2^16
   const int64_t xs_bytes = P * 16 * 2;
   if (xs_bytes >= (int64_t)kOOB || P * 64 * 2 >= (int64_t)kOOB) return false;
   StreamArgs a{};

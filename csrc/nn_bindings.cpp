@@ -776,7 +776,9 @@ at::Tensor conv_f32_fwd(at::Tensor x, at::Tensor w, int64_t pad, int64_t stride,
   TORCH_CHECK(stride >= 1 && pad >= 0, "conv_f32_fwd: bad stride / padding");
   const int OH = (H + 2 * (int)pad - R) / (int)stride + 1, OW = (W + 2 * (int)pad - S) / (int)stride + 1;
   TORCH_CHECK(OH > 0 && OW > 0, "conv_f32_fwd: empty output");
-  TORCH_CHECK(conv_f32_supported(C, Cout, (int64_t)N * OH * OW, R * S * C),
+  TORCH_CHECK(conv_f32_divisors_ok(OH, OW, C, S), "conv_f32_fwd: OH, OW, C and S must be below 65536");
+  const int64_t K = (int64_t)R * S * C;  // R is bounded by OH > 0 (R <= H + 2 pad), S and C by the line above
+  TORCH_CHECK(K < (1 << 24) && conv_f32_supported(C, Cout, (int64_t)N * OH * OW, (int)K),
               "conv_f32_fwd: needs C % 4 == 0, Cout % 4 == 0 and fewer than 2^24 output pixels");
   at::Tensor y;
   if (opt(out)) {
@@ -799,8 +801,12 @@ at::Tensor conv_f32_wgrad(at::Tensor dy, at::Tensor x, int64_t R, int64_t S, int
   const int OH = (H + 2 * (int)pad - (int)R) / (int)stride + 1, OW = (W + 2 * (int)pad - (int)S) / (int)stride + 1;
   TORCH_CHECK(dy.size(0) == N && dy.size(2) == OH && dy.size(3) == OW, "conv_f32_wgrad: dy shape does not match x");
   const int64_t M = (int64_t)N * OH * OW;
-  const int K = (int)(R * S * C);
-  TORCH_CHECK(conv_f32_supported(C, Cout, M, K), "conv_f32_wgrad: needs C % 4 == 0, Cout % 4 == 0, M < 2^24");
+  TORCH_CHECK(S >= 1 && R >= 1 && S < 65536 && R < 65536 && conv_f32_divisors_ok(OH, OW, C, (int)S),
+              "conv_f32_wgrad: OH, OW, C and S must be below 65536");
+  const int64_t K64 = R * S * C;  // each factor below 2^16 by the line above
+  TORCH_CHECK(K64 < (1 << 24) && conv_f32_supported(C, Cout, M, (int)K64),
+              "conv_f32_wgrad: needs C % 4 == 0, Cout % 4 == 0, M < 2^24");
+  const int K = (int)K64;
   at::Tensor dw = at::empty({Cout, R, S, C}, x.options());
   const int splits = conv_f32_wgrad_splits(M, Cout, K);
   at::Tensor part = at::empty({(int64_t)splits * Cout * K}, x.options());
@@ -990,6 +996,10 @@ std::vector<at::Tensor> stem_fwd(at::Tensor x, at::Tensor wpk, bool want_stats) 
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;  // 7x7 / s2 / p3
   const int64_t P = (int64_t)N * OH * OW;
   TORCH_CHECK(P < (1 << 24), "stem_fwd: too many output pixels for 24-bit index math");
+  // mm::fdiv decodes the output pixel with the folded width and height as divisors (exact for divisor < 2^16)
+  TORCH_CHECK(OH < 65536 && OW < 65536, "stem_fwd: the folded BH, BW must be below 65536");
+  TORCH_CHECK(P * Cout * 2 < (int64_t(1) << 31),
+              "stem_fwd: the output reaches the 2 GiB buffer-descriptor range (lower the per-GPU batch)");
   at::Tensor xs = at::empty({N, OH, OW, 16}, x.options().memory_format(at::MemoryFormat::Contiguous));
   launch_stem_fold(x.data_ptr(), xs.data_ptr(), N, H, W, current_stream(x));
   at::Tensor y = at::empty({N, Cout, OH, OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
@@ -1019,6 +1029,7 @@ at::Tensor stem_wgrad_bn(at::Tensor dy_pool, at::Tensor pos, at::Tensor x, at::T
               "stem_wgrad_bn: x / xs / dy_pool / image size mismatch");
   TORCH_CHECK(stem_wgrad_bn_eligible(N, (int)H, (int)W, Cout, OH, OW),
               "stem_wgrad_bn: needs 64 channels, an even conv output and a 3x3 / s2 / p1 pool");
+  TORCH_CHECK(xs.size(1) < 65536 && xs.size(2) < 65536, "stem_wgrad_bn: the folded BH, BW must be below 65536");
   const int splits = stem_wgrad_bn_splits(N, (int)H, (int)W);
   at::Tensor part = at::empty({(int64_t)splits * Cout * 256}, xs.options().dtype(at::kFloat));
   at::Tensor dw = at::empty({Cout, 256}, xs.options().dtype(out_dtype));
@@ -1036,6 +1047,7 @@ at::Tensor stem_wgrad(at::Tensor dy, at::Tensor xs, int64_t H, int64_t W, c10::S
   const int N = (int)xs.size(0), Cout = (int)dy.size(1);
   TORCH_CHECK(xs.size(1) == (H + 1) / 2 && xs.size(2) == (W + 1) / 2, "stem_wgrad: xs / image size mismatch");
   TORCH_CHECK((int64_t)N * xs.size(1) * xs.size(2) < (1 << 24), "stem_wgrad: too many output pixels");
+  TORCH_CHECK(xs.size(1) < 65536 && xs.size(2) < 65536, "stem_wgrad: the folded BH, BW must be below 65536");
   TORCH_CHECK(dy.size(0) == N && dy.size(2) == xs.size(1) && dy.size(3) == xs.size(2), "stem_wgrad: dy shape");
   const int splits = stem_wgrad_splits(N, (int)H, (int)W, Cout);
   at::Tensor part = at::empty({(int64_t)splits * Cout * 256}, xs.options().dtype(at::kFloat));
@@ -1092,6 +1104,10 @@ static void check_conv3(const at::Tensor& x, const at::Tensor& w) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0,
               "conv3x3: 16-byte aligned operands required");
   TORCH_CHECK(x.numel() / x.size(1) < (1 << 24), "conv3x3: too many pixels for 24-bit index math");
+  // the pixel decode divides by W, then H, and the k decode by Cin (data gradients: Cout) with mm::fdiv, which is
+  // exact only for a divisor below 2^16
+  TORCH_CHECK(x.size(2) < 65536 && x.size(3) < 65536 && x.size(1) < 65536 && w.size(0) < 65536,
+              "conv3x3: H, W, Cin and Cout must be below 65536");
   check_span(x, "conv3x3 input");
   TORCH_CHECK(x.numel() / x.size(1) * w.size(0) * 2 < (int64_t(1) << 31),
               "conv3x3: the output reaches the 2 GiB buffer-descriptor range (lower the per-GPU batch)");
@@ -1194,10 +1210,13 @@ at::Tensor conv3x3_wgrad(at::Tensor dy, at::Tensor x, int64_t stride, c10::Scala
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 && dy.size(1) % 8 == 0,
               "conv3x3_wgrad: dy must be a bf16 GPU tensor, Cout % 8");
   TORCH_CHECK(x.numel() / x.size(1) < (1 << 24), "conv3x3_wgrad: too many pixels");
+  TORCH_CHECK(x.size(2) < 65536 && x.size(3) < 65536, "conv3x3_wgrad: H and W must be below 65536");
+  check_span(x, "conv3x3_wgrad x");
+  check_span(dy, "conv3x3_wgrad dy");
   const int N = (int)x.size(0), Cin = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), Cout = (int)dy.size(1);
   TORCH_CHECK(dy.size(2) == (H - 1) / stride + 1 && dy.size(3) == (W - 1) / stride + 1, "conv3x3_wgrad: dy shape");
   at::Tensor dw = at::empty({Cout, Cin, 3, 3}, x.options().dtype(out_dtype).memory_format(at::MemoryFormat::ChannelsLast));
-  if (halo_wgrad_eligible(Cin, Cout, W, (int)stride) && (int64_t)N * (H + 2) * (W + 2) < (1 << 30)) {
+  if (halo_wgrad_serves(N, H, W, Cin, Cout, (int)stride)) {
     const int hs = halo_wgrad_splits(N, H, W);
     at::Tensor hpart = at::empty({(int64_t)hs * Cout * 9 * Cin}, x.options().dtype(at::kFloat));
     launch_conv3x3_halo_wgrad(dy.data_ptr(), x.data_ptr(), hpart.data_ptr<float>(), hs, dw.data_ptr(), out_code, N, H, W,
@@ -1311,6 +1330,10 @@ void bind_nn(pybind11::module& m) {
   m.def("gemm_tn_splits", [](int64_t Mo, int64_t No, int64_t K) { return gemm_tn_splits((int)Mo, (int)No, (int)K); },
         "split-K count of a weight-gradient gemm_tn launch");
   m.def("set_halo_wgrad", &set_halo_wgrad, "halo 64-channel 3x3 weight gradient: -1 environment (default on), 0 off, 1 on");
+  m.def("halo_wgrad_serves", [](int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t stride) {
+        return N < (1LL << 31) && H < (1LL << 31) && W < (1LL << 31) &&
+               halo_wgrad_serves((int)N, (int)H, (int)W, (int)Cin, (int)Cout, (int)stride); },
+        "whether conv3x3_wgrad runs this geometry on the halo kernel (eligible channels / width and index ranges)");
   m.def("halo_wgrad_eligible", [](int64_t Cin, int64_t Cout, int64_t W, int64_t stride) {
         return halo_wgrad_eligible((int)Cin, (int)Cout, (int)W, (int)stride); });
   m.def("halo_conv_eligible", [](int64_t Cin, int64_t Cout, int64_t W, int64_t stride, bool fwd) {

@@ -577,6 +577,8 @@ def supported3x3(x: torch.Tensor, conv: nn.Conv2d) -> bool:
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
             and _conv3_channels_ok(conv) and x.is_contiguous(memory_format=torch.channels_last)
             and _limits.pixels_ok(x.numel() // x.shape[1], "conv3x3")
+            and _limits.divisors_ok({"H": x.shape[2], "W": x.shape[3], "Cin": x.shape[1], "Cout": conv.out_channels},
+                                    "conv3x3")
             and _limits.span_ok(max(x.numel(), x.numel() // x.shape[1] // conv.stride[0] ** 2 * conv.out_channels)
                                 * x.element_size(), "conv3x3 operand"))
 
@@ -674,7 +676,8 @@ def supported_stem(x: torch.Tensor, conv: nn.Conv2d) -> bool:
             and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.out_channels % 64 == 0
             and x.is_contiguous(memory_format=torch.channels_last)
-            and _limits.pixels_ok(x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2), "stem conv"))
+            and _limits.pixels_ok(x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2), "stem conv")
+            and _limits.divisors_ok({"folded H": (x.shape[2] + 1) // 2, "folded W": (x.shape[3] + 1) // 2}, "stem conv"))
 
 
 def stem_pack_weight(w: torch.Tensor) -> torch.Tensor:

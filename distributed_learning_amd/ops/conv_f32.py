@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
+from . import limits as _limits
 
 CL = torch.channels_last
 
@@ -40,15 +41,20 @@ def supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
     if conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] or conv.padding[0] != conv.padding[1]:
         return False
     cin, cout = x.shape[1], conv.out_channels
+    oh = (x.shape[2] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
+    ow = (x.shape[3] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
+    # the kernels divide by OW, OH (pixel decode) and C, S (k decode); the data gradient is the forward kernel over
+    # dy, whose divisors are H, W and Cout. The space-to-depth stem runs a 4x4 conv over the 2x2-block image (about
+    # H / 2 x W / 2, 12 channels): the unfolded extents checked here are larger than any of its divisors, so the same
+    # bound is on the safe side there
+    dims = {"H": x.shape[2], "W": x.shape[3], "OH": oh, "OW": ow, "Cin": cin, "Cout": cout, "kernel": conv.kernel_size[1]}
     if cin == 3 and STEM_NATIVE and stem_s2d_ok(x, conv):
-        return True
+        return _limits.divisors_ok(dims, "fp32 conv")
     if cout % 4 or not (cin % 4 == 0 or (cin == 3 and STEM_NATIVE)):
         return False
     if conv.stride[0] != 1 and x.requires_grad:
         return False
-    oh = (x.shape[2] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
-    ow = (x.shape[3] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
-    return x.shape[0] * oh * ow < (1 << 24) and x.numel() * 4 < (1 << 31)
+    return x.shape[0] * oh * ow < (1 << 24) and x.numel() * 4 < (1 << 31) and _limits.divisors_ok(dims, "fp32 conv")
 
 
 def nhwc_view_ok(x: torch.Tensor) -> bool:

@@ -10,6 +10,11 @@ Two ranges bound the hand-written kernels:
   slots use offset 0x80000000 (``kOOB``), so every operand must span fewer than 2^31 bytes
   (checked again in the C++ bindings, csrc/nn_bindings.cpp ``check_span``).
 
+A third bound follows from the same divisions: ``fdiv(n, d)`` is ``n // d`` only for n < 2^24 **and d < 2^16**
+(d = 66011, n = 254 * 66011 - 1 < 2^24 gives 254, not 253), so every extent a kernel divides by -- H, W (for the
+stem the folded (H + 1) // 2, (W + 1) // 2) and the channel count of the k -> (tap, channel) decode -- must stay
+below 65536 (``divisors_ok``).
+
 Crossing either range raises :class:`NativeLimitError` naming the operand; nothing silently falls
 back to a different (slower) kernel mid-model and nothing computes with wrapped indices.
 """
@@ -17,6 +22,7 @@ from __future__ import annotations
 
 PIXEL_LIMIT = 1 << 24
 SPAN_LIMIT = 1 << 31
+DIVISOR_LIMIT = 1 << 16
 
 
 class NativeLimitError(RuntimeError):
@@ -38,4 +44,14 @@ def span_ok(nbytes: int, what: str) -> bool:
         raise NativeLimitError(
             f"{what}: {nbytes} bytes >= 2 GiB, beyond the native kernels' buffer-descriptor range; lower the "
             f"per-GPU batch or run with --kernels torch")
+    return True
+
+
+def divisors_ok(dims: dict, what: str) -> bool:
+    """True, or raises when an extent in ``dims`` (name -> value) that ``what`` divides by reaches 2^16."""
+    for name, d in dims.items():
+        if d >= DIVISOR_LIMIT:
+            raise NativeLimitError(
+                f"{what}: {name} = {d} >= 65536, beyond the divisor range of the native kernels' 24-bit index math; "
+                f"use a smaller image or run with --kernels torch")
     return True

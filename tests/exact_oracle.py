@@ -279,6 +279,56 @@ def mask_bits(mask: torch.Tensor, n_elems: int) -> torch.Tensor:
     return torch.stack([(m >> j) & 1 for j in range(8)], 1).reshape(-1)[:n_elems]
 
 
+# ------------------------------------------------------------------ device generators (index-edge operands)
+# Operands of 10^8 .. 10^9 elements (test_gpu_index_edges.py) are drawn on the device: the CPU generators above
+# would take minutes there. Same value ranges, and the same worst-case checks (``check_dense``; for reductions over
+# millions of rows ``check_exact_sum`` on a bound taken from the data actually drawn).
+def dev_gen(seed: int, device) -> torch.Generator:
+    return torch.Generator(device=device).manual_seed(int(seed))
+
+
+DEV_BLOCK = 1 << 27  # elements drawn at a time: the int8 draw and its masks stay a fraction of the operand
+
+
+def _dev_fill(shape, g: torch.Generator, dtype, draw) -> torch.Tensor:
+    out = torch.empty(tuple(shape), dtype=dtype, device=g.device)
+    flat = out.view(-1)
+    for i in range(0, flat.numel(), DEV_BLOCK):
+        n = min(DEV_BLOCK, flat.numel() - i)
+        flat[i:i + n] = draw(n)
+    return out
+
+
+def dev_ints(shape, g: torch.Generator, lo: int, hi: int, dtype=torch.bfloat16) -> torch.Tensor:
+    """Integers in [lo, hi] (within int8) on the generator's device."""
+    assert -128 <= lo <= hi <= 127
+    return _dev_fill(shape, g, dtype,
+                     lambda n: torch.randint(lo, hi + 1, (n,), generator=g, device=g.device, dtype=torch.int8))
+
+
+def dev_dense(shape, g: torch.Generator, k_total: int, dtype=torch.bfloat16) -> torch.Tensor:
+    """A dense-regime operand, integers in [-3, 3], for a reduction of length ``k_total`` (checked)."""
+    check_dense(k_total)
+    return dev_ints(shape, g, -DENSE_MAX, DENSE_MAX, dtype)
+
+
+def dev_sparse_signs(shape, g: torch.Generator, one_in: int, dtype=torch.bfloat16) -> torch.Tensor:
+    """+-1 at about one element in ``one_in``, zero elsewhere, at independent positions."""
+    assert 1 <= one_in <= 63
+
+    def draw(n):
+        r = torch.randint(0, 2 * one_in, (n,), generator=g, device=g.device, dtype=torch.int8)
+        return (r == 0).to(torch.int8) - (r == 1).to(torch.int8)
+
+    return _dev_fill(shape, g, dtype, draw)
+
+
+def check_exact_sum(bound, what: str = "reduction") -> None:
+    """``bound``: an upper bound of the sum of |products| of the longest reduction, taken from the data drawn."""
+    if not float(bound) < EXACT_LIMIT:
+        raise ValueError(f"{what}: sum of |products| may reach {float(bound):.0f} >= 2^24, fp32 partial sums may round")
+
+
 # -------------------------------------------------------------------------------------------- references
 def integral(ref: torch.Tensor, limit: int = EXACT_LIMIT, what: str = "reference") -> torch.Tensor:
     """The float64 reference must be integer-valued and within the exactly representable range."""
@@ -303,6 +353,74 @@ def conv_dgrad_ref(x_shape, w, dy, stride=1, pad=1) -> torch.Tensor:
 
 def conv_wgrad_ref(x, w_shape, dy, stride=1, pad=1) -> torch.Tensor:
     return integral(torch.nn.grad.conv2d_weight(x.double().cpu(), tuple(w_shape), dy.double().cpu(), stride, pad))
+
+
+TN_BLOCK = 1 << 19
+
+
+def tn_ref(a: torch.Tensor, b: torch.Tensor, groups: int = 1024) -> torch.Tensor:
+    """a[P, M]^T b[P, N] in float64 for a reduction over millions of rows. The rows are split into ``groups`` batch
+    entries that are summed afterwards: a plain matmul with an 8 x 8 output would run its whole reduction in one
+    workgroup. Integer operands: exact in any grouping."""
+    out = torch.zeros(a.shape[1], b.shape[1], dtype=torch.float64, device=a.device)
+    for i in range(0, a.shape[0], TN_BLOCK):  # float64 copies of one block at a time
+        ab, bb = a[i:i + TN_BLOCK].double(), b[i:i + TN_BLOCK].double()
+        P = ab.shape[0]
+        g = max(1, min(groups, P // 64))
+        main = P // g * g
+        out += torch.bmm(ab[:main].reshape(g, -1, ab.shape[1]).transpose(1, 2), bb[:main].reshape(g, -1, bb.shape[1])).sum(0)
+        if main < P:
+            out += ab[main:].t() @ bb[main:]
+    return out
+
+
+def nonzeros_per_column(t: torch.Tensor, block_rows: int = 0) -> torch.Tensor:
+    """Nonzero count of every column of the [rows, C] view of ``t``, in row blocks of 2^24 elements (a whole-tensor
+    ``sum`` of the boolean would be carried out in int64: 8 bytes per element of a 10^9-element operand)."""
+    r = rows_view(t)
+    block_rows = block_rows or max(1, (1 << 24) // r.shape[1])
+    n = torch.zeros(r.shape[1], dtype=torch.int64, device=r.device)
+    for i in range(0, r.shape[0], block_rows):
+        n += (r[i:i + block_rows] != 0).sum(0)
+    return n
+
+
+def conv_ref_dev(x, w, stride=1, pad=1) -> torch.Tensor:
+    """``conv_ref`` where the operands live (no copy to the host, no convolution library): float64, tap by tap,
+    y[n, :, oh, ow] += x[n, :, oh s + kh - pad, ow s + kw - pad] w[:, :, kh, kw]^T. For slices of large operands."""
+    N, Ci, H, W = x.shape
+    Co, k = w.shape[0], w.shape[2]
+    OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    xb = F.pad(x.permute(0, 2, 3, 1).double(), (0, 0, pad, pad, pad, pad))
+    wd = w.double().to(x.device)
+    y = torch.zeros(N, OH, OW, Co, dtype=torch.float64, device=x.device)
+    for kh in range(k):
+        for kw in range(k):
+            t = xb[:, kh:kh + (OH - 1) * stride + 1:stride, kw:kw + (OW - 1) * stride + 1:stride, :]
+            y += t @ wd[:, :, kh, kw].t()
+    return integral(y.permute(0, 3, 1, 2))
+
+
+def conv_wgrad_ref_dev(dy, x, k, stride, pad, block_pixels=1 << 21) -> torch.Tensor:
+    """``conv_wgrad_ref`` where the operands live, for reductions over millions of pixels: float64 [Cout, C, k, k],
+    tap by tap over blocks of output rows, dw[co, c, kh, kw] = sum_p dy[p, co] x[c, oh s + kh - pad, ow s + kw - pad].
+    Integer operands: every partial sum is exact in float64."""
+    N, Co, OH, OW = dy.shape
+    Ci, H = x.shape[1], x.shape[2]
+    dw = torch.zeros(Co, Ci, k, k, dtype=torch.float64, device=dy.device)
+    rows_per = max(1, block_pixels // OW)
+    for n in range(N):
+        for r0 in range(0, OH, rows_per):
+            r1 = min(OH, r0 + rows_per)
+            d = dy[n, :, r0:r1, :].permute(1, 2, 0).reshape(-1, Co).double()
+            lo, hi = r0 * stride - pad, (r1 - 1) * stride - pad + k  # input rows [lo, hi), may leave the image
+            xb = x[n, :, max(lo, 0):min(hi, H), :].permute(1, 2, 0).double()  # [rows, W, C]
+            xb = F.pad(xb, (0, 0, pad, pad, max(0, -lo), max(0, hi - H)))
+            for kh in range(k):
+                for kw in range(k):
+                    t = xb[kh:kh + (r1 - r0 - 1) * stride + 1:stride, kw:kw + (OW - 1) * stride + 1:stride, :]
+                    dw[:, :, kh, kw] += tn_ref(d, t.reshape(-1, Ci))
+    return integral(dw, what="weight gradient reference")
 
 
 def round_bf16(ref: torch.Tensor) -> torch.Tensor:
@@ -382,3 +500,35 @@ def assert_exact(got: torch.Tensor, ref: torch.Tensor, tile=None, what: str = ""
     msg = mismatch_report(got, ref, tile, what)
     if msg is not None:
         raise AssertionError(msg)
+
+
+def assert_exact_block(got: torch.Tensor, ref: torch.Tensor, what: str = "", row0: int = 0, total_rows=None,
+                       tile_rows: int = 128, first: int = 6) -> None:
+    """``assert_exact`` for a block of a large operand, compared where it lives (nothing but the few reported
+    elements is copied to the host). ``got`` / ``ref``: the same rows [row0, row0 + rows) of the [total_rows, C] GEMM
+    view (4-D channels-first tensors are read as their pixel rows). The failure names the element and byte offsets in
+    the whole operand, the ``tile_rows``-row tiles touched and how many mismatches lie on the last row tile."""
+    g2, r2 = rows_view(got.detach()), rows_view(ref.detach()).to(got.device)
+    assert tuple(g2.shape) == tuple(r2.shape), f"{what}: shape {tuple(g2.shape)} != expected {tuple(r2.shape)}"
+    if g2.dtype == r2.dtype and torch.equal(g2, r2):
+        return
+    bad = g2.double() != r2.double()  # NaN never equal, signed zero irrelevant
+    if not bool(bad.any()):
+        return
+    idx = bad.nonzero()
+    n, cols, esz = int(idx.shape[0]), int(g2.shape[1]), got.element_size()
+    total = int(total_rows) if total_rows is not None else row0 + int(g2.shape[0])
+    rows = idx[:, 0] + row0
+    lo, hi = int(rows.min()), int(rows.max())
+    last_tile = (total - 1) // tile_rows
+    on_last = int((rows // tile_rows == last_tile).sum())
+    head = []
+    for r, c in idx[:first].tolist():
+        e = (row0 + r) * cols + c
+        head.append(f"row {row0 + r} col {c} (element {e}, byte {e * esz}, row tile {(row0 + r) // tile_rows}): "
+                    f"got {float(g2[r, c]):g} expected {float(r2[r, c]):g}")
+    raise AssertionError(
+        f"{what}: {n} of {g2.numel()} elements of rows [{row0}, {row0 + g2.shape[0]}) differ; first " + "; ".join(head)
+        + f"; rows {lo}..{hi} (element offsets {lo * cols}..{(hi + 1) * cols - 1}), {tile_rows}-row tiles "
+        f"{lo // tile_rows}..{hi // tile_rows}; {on_last} on the last row tile {last_tile} "
+        f"({total - last_tile * tile_rows} rows, from element {last_tile * tile_rows * cols})")

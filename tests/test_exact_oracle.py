@@ -298,3 +298,67 @@ def test_injected_conv_defect_is_caught_and_the_norm_criterion_passes_it():
         xo.assert_exact(got, exp, (128, 128), "tap dropped at the right border")
     assert "bounding box [0, 0, 4, 11]" in str(e.value) or "bounding box [0, 1, 4, 11]" in str(e.value), str(e.value)
     assert float((got.double() - y32.double()).norm() / y32.double().norm()) < 1e-2  # test_gpu_conv3x3.py's bound
+
+
+# -------------------------------------------------------------- device generators and the block comparison
+def test_device_generators_keep_the_regimes_bounds():
+    g = xo.dev_gen(3, "cpu")
+    t = xo.dev_dense((1000, 64), g, 64)
+    assert t.dtype == torch.bfloat16 and float(t.abs().max()) == 3 and bool((t == t.round()).all())
+    with pytest.raises(ValueError, match="dense regime"):
+        xo.dev_dense((4, 4), g, 1 << 22)
+    s = xo.dev_sparse_signs((1 << 16, 8), g, 32)
+    assert set(s.unique().tolist()) == {-1.0, 0.0, 1.0}
+    share = float((s != 0).float().mean())
+    assert 0.8 / 32 < share < 1.25 / 32
+    assert torch.equal(xo.dev_ints((64,), xo.dev_gen(5, "cpu"), -2, 2), xo.dev_ints((64,), xo.dev_gen(5, "cpu"), -2, 2))
+    xo.check_exact_sum((1 << 24) - 1)
+    with pytest.raises(ValueError, match="2\\^24"):
+        xo.check_exact_sum(1 << 24)
+
+
+def test_assert_exact_block_names_offsets_and_the_last_row_tile():
+    ref = torch.arange(300 * 8, dtype=torch.float32).view(300, 8).to(torch.bfloat16)
+    xo.assert_exact_block(ref.clone(), ref, "same")
+    xo.assert_exact_block(ref.clone(), ref.double(), "same value, other dtype")
+    z = torch.zeros(4, 8)
+    xo.assert_exact_block(-z, z, "signed zero")
+    got = ref.clone()
+    got[299, 7] = 1.0  # global row 1299 of 1300: the last (ragged, 20-row) tile of 128 rows
+    with pytest.raises(AssertionError) as e:
+        xo.assert_exact_block(got, ref, "block", row0=1000, total_rows=1300)
+    msg = str(e.value)
+    assert "row 1299 col 7 (element 10399, byte 20798, row tile 10)" in msg
+    assert "1 on the last row tile 10 (20 rows, from element 10240)" in msg
+    nan = ref.clone()
+    nan[0, 0] = float("nan")
+    with pytest.raises(AssertionError, match="1 of 2400 elements"):
+        xo.assert_exact_block(nan, nan.clone(), "NaN is never equal")
+    img = torch.zeros(2, 8, 3, 5)
+    bad = img.clone()
+    bad[1, 2, 2, 4] = 1
+    with pytest.raises(AssertionError, match=r"row 29 col 2 \(element 234"):
+        xo.assert_exact_block(bad, img, "4-D blocks are read as pixel rows")
+
+
+@pytest.mark.parametrize("k,stride,pad", [(3, 1, 1), (3, 2, 1), (7, 2, 3), (1, 1, 0)])
+def test_device_references_are_the_library_references(k, stride, pad):
+    """conv_ref_dev / conv_wgrad_ref_dev (float64 tap by tap, for slices and reductions of the index-edge operands)
+    against F.conv2d / conv2d_weight in float64; the weight gradient also in blocks of a few rows."""
+    g = xo.gen(k + stride)
+    x, w = xo.ints((2, 5, 9, 12), g, -3, 3), xo.ints((6, 5, k, k), g, -3, 3)
+    ref = xo.conv_ref(x, w, stride, pad)
+    assert torch.equal(xo.conv_ref_dev(x, w, stride, pad), ref)
+    dy = xo.ints(ref.shape, g, -2, 2)
+    wref = xo.conv_wgrad_ref(x, w.shape, dy, stride, pad)
+    assert torch.equal(xo.conv_wgrad_ref_dev(dy, x, k, stride, pad), wref)
+    assert torch.equal(xo.conv_wgrad_ref_dev(dy, x, k, stride, pad, block_pixels=2 * ref.shape[3]), wref)
+
+
+def test_grouped_reduction_and_column_counts():
+    g = xo.gen(2)
+    for P in (1, 63, 64, 1000, 70001):
+        a, b = xo.ints((P, 8), g, -3, 3), xo.ints((P, 5), g, -3, 3)
+        assert torch.equal(xo.tn_ref(a, b), a.double().t() @ b.double())
+    t = xo.ints((3, 8, 5, 7), g, -1, 1).contiguous(memory_format=torch.channels_last)
+    assert torch.equal(xo.nonzeros_per_column(t, block_rows=16), (t != 0).sum((0, 2, 3)))

@@ -256,3 +256,86 @@ def test_addend2_refuses_rows_outside_the_fast_division(args, cuda, op, n, h, w)
             args.C.gemm_nt_bn(A, Bk, None, True, torch.zeros(m, c, dtype=BF, device=cuda), torch.zeros(7 * c, device=cuda),
                               None, 1, None, a2, h, w)
     torch.cuda.synchronize()
+
+
+# ---- the divisor bound of the multiply-shift decodes (mm::fdiv: dividend < 2^24 AND divisor < 2^16) in the conv, stem
+# and fp32-conv bindings. These checks follow the device check, so tests/test_binding_checks.py cannot see them; the
+# operands are uninitialised and nothing is launched. The same refusals at 2^24 pixels and 2^31 bytes:
+# tests/test_gpu_index_edges.py ----
+def _cl_empty(dev, n, c, h, w, dtype=BF):
+    return torch.empty(n, h, w, c, dtype=dtype, device=dev).permute(0, 3, 1, 2)
+
+
+# [1, 8, 254, 66011] is the geometry whose last pixel decodes to a row outside the image (tests/test_index_domain.py)
+DIVISOR_REFUSED = [(1, 8, 254, 66011), (1, 8, 66011, 254), (1, 8, 1, 65536), (1, 8, 65536, 1)]
+
+
+@pytest.mark.parametrize("shape", DIVISOR_REFUSED)
+def test_conv3x3_refuses_divisors_outside_the_fast_division(args, cuda, shape):
+    x = _cl_empty(cuda, *shape)
+    w = torch.empty(8, 8, 3, 3, dtype=BF, device=cuda).contiguous(memory_format=torch.channels_last)
+    ws = torch.zeros(7 * 8, device=cuda)
+    for call in (lambda: args.C.conv3x3_fwd(x, w, 1, True), lambda: args.C.conv3x3_dgrad(x, w),
+                 lambda: args.C.conv3x3_dgrad_bn(x, w, None, x, ws, None, 1)):
+        with pytest.raises(RuntimeError, match="conv3x3: H, W, Cin and Cout must be below 65536"):
+            call()
+    with pytest.raises(RuntimeError, match="conv3x3_wgrad: H and W must be below 65536"):
+        args.C.conv3x3_wgrad(x, x, 1, F32)
+    torch.cuda.synchronize()
+
+
+def test_conv3x3_accepts_the_largest_divisor(args, cuda):
+    """[1, 8, 1, 65535]: one step inside the bound the call runs (and test_gpu_index_edges.py checks what it computes
+    at [1, 8, 255, 65535])."""
+    x = torch.zeros(1, 1, 65535, 8, dtype=BF, device=cuda).permute(0, 3, 1, 2)
+    w = torch.zeros(8, 8, 3, 3, dtype=BF, device=cuda).contiguous(memory_format=torch.channels_last)
+    y, _ = args.C.conv3x3_fwd(x, w, 1, False)
+    assert y.shape == (1, 8, 1, 65535) and not bool(y.any())
+
+
+def test_channel_divisors_are_refused(args, cuda):
+    """The k -> (tap, channel) decode divides by Cin (data gradient: Cout)."""
+    x = _cl_empty(cuda, 1, 65536, 2, 2)
+    w = torch.empty(8, 65536, 3, 3, dtype=BF, device=cuda).contiguous(memory_format=torch.channels_last)
+    with pytest.raises(RuntimeError, match="conv3x3: H, W, Cin and Cout must be below 65536"):
+        args.C.conv3x3_fwd(x, w, 1, False)
+    with pytest.raises(RuntimeError, match="conv3x3: H, W, Cin and Cout must be below 65536"):
+        args.C.conv3x3_dgrad(_cl_empty(cuda, 1, 8, 2, 2), w)  # dy [1, 8, 2, 2] -> dx [1, 65536, 2, 2]
+    xf = _cl_empty(cuda, 1, 65536, 2, 2, F32)
+    with pytest.raises(RuntimeError, match="conv_f32_fwd: OH, OW, C and S must be below 65536"):
+        args.C.conv_f32_fwd(xf, torch.empty(4, 1, 1, 65536, device=cuda), 0, 1)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("h,w", [(508, 132022), (2, 131072), (131071, 2)])
+def test_stem_refuses_folded_sizes_outside_the_fast_division(args, cuda, h, w):
+    """The stem decodes over the folded image [(H + 1) / 2, (W + 1) / 2]; 508 x 132022 folds to 254 x 66011."""
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    with pytest.raises(RuntimeError, match="stem_fwd: the folded BH, BW must be below 65536"):
+        args.C.stem_fwd(_cl_empty(cuda, 1, 3, h, w), torch.empty(64, 256, dtype=BF, device=cuda), True)
+    xs = torch.empty(1, oh, ow, 16, dtype=BF, device=cuda)
+    with pytest.raises(RuntimeError, match="stem_wgrad: the folded BH, BW must be below 65536"):
+        args.C.stem_wgrad(_cl_empty(cuda, 1, 64, oh, ow), xs, h, w, F32)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("shape", [(1, 4, 254, 66011), (1, 4, 1, 65536), (1, 4, 65536, 1)])
+def test_conv_f32_refuses_divisors_outside_the_fast_division(args, cuda, shape):
+    x = _cl_empty(cuda, *shape, dtype=F32)
+    with pytest.raises(RuntimeError, match="conv_f32_fwd: OH, OW, C and S must be below 65536"):
+        args.C.conv_f32_fwd(x, torch.empty(4, 3, 3, 4, device=cuda), 1, 1)
+    with pytest.raises(RuntimeError, match="conv_f32_wgrad: OH, OW, C and S must be below 65536"):
+        args.C.conv_f32_wgrad(x, x, 3, 3, 1, 1)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("h,w", [(131072, 4), (4, 131072)])
+def test_stem_wgrad_bn_refuses_folded_sizes_outside_the_fast_division(args, cuda, h, w):
+    """The fused form walks 2x2 quads of the folded image with divisors BW / 2 and BH / 2; same bound as stem_wgrad."""
+    bh, bw = h // 2, w // 2
+    dyp = _cl_empty(cuda, 1, 64, bh // 2, bw // 2)
+    pos = torch.empty(1, bh // 2, bw // 2, 64, dtype=torch.uint8, device=cuda).permute(0, 3, 1, 2)
+    xs = torch.empty(1, bh, bw, 16, dtype=BF, device=cuda)
+    with pytest.raises(RuntimeError, match="stem_wgrad_bn: the folded BH, BW must be below 65536"):
+        args.C.stem_wgrad_bn(dyp, pos, _cl_empty(cuda, 1, 64, bh, bw), torch.zeros(7 * 64, device=cuda), xs, h, w, F32)
+    torch.cuda.synchronize()
