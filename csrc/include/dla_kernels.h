@@ -144,6 +144,18 @@ void launch_augment_mix(const uint8_t* src, void* out, int dtype, const float* g
                         const int32_t* partner, const float* lam, const int32_t* box, const float* scale,
                         const float* bias, int N, int Hs, int Ws, int Ho, int Wo, int pad, bool blend,
                         hipStream_t stream);
+// Indexed forms: `store` is [P][Hs][Ws][3] of any size (64-bit per-image base, 32-bit offsets inside an image) and
+// batch image n is store row min(uint32(index[n]), P - 1), index a device int32 [N]; partner[n] stays a position in
+// the batch, whose image is row index[partner[n]] sampled with geom[partner[n]] and flip[partner[n]]. The result
+// is what the forms above give for the gathered batch store[index]. Hs*Ws*3 and N*Ho*Wo*3 must be below 2^31, an
+// image at least three pixels and 1 <= P < 2^31.
+void launch_augment_gather(const uint8_t* store, int64_t P, const int32_t* index, void* out, int dtype,
+                           const float* geom, const uint8_t* flip, const float* scale, const float* bias, int N,
+                           int Hs, int Ws, int Ho, int Wo, int pad, hipStream_t stream);
+void launch_augment_mix_gather(const uint8_t* store, int64_t P, const int32_t* index, void* out, int dtype,
+                               const float* geom, const uint8_t* flip, const int32_t* partner, const float* lam,
+                               const int32_t* box, const float* scale, const float* bias, int N, int Hs, int Ws,
+                               int Ho, int Wo, int pad, bool blend, hipStream_t stream);
 
 // ---- fused log-softmax + NLL (loss.hip) -----------------------------------------------------
 // logits [B, C] (dtype), target [B] int64 (< 0 = ignored). ws: 3*B floats (row lse, row loss,

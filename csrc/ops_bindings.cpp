@@ -478,10 +478,11 @@ struct AugmentDims {
   int N, Hs, Ws, Ho, Wo, dtype;
 };
 
-// The checks augment_ and augment_mix_ share; `op` prefixes the messages.
+// The checks the augment bindings share; `op` prefixes the messages. With `index` (the indexed forms) src is a
+// store [P, Hs, Ws, 3] of any size, N is out's and index's length and the 2^31 limit applies to one image.
 static AugmentDims check_augment_args(const char* op, const at::Tensor& src, const at::Tensor& out,
                                       const at::Tensor& geom, const at::Tensor& flip, const at::Tensor& scale,
-                                      const at::Tensor& bias, int64_t pad) {
+                                      const at::Tensor& bias, int64_t pad, const at::Tensor* index = nullptr) {
   TORCH_CHECK(src.is_cuda() && out.is_cuda() && geom.is_cuda() && flip.is_cuda() && scale.is_cuda() && bias.is_cuda(),
               op, ": every tensor must be on the GPU");
   for (const at::Tensor* t : {&out, &geom, &flip, &scale, &bias})
@@ -490,9 +491,17 @@ static AugmentDims check_augment_args(const char* op, const at::Tensor& src, con
   TORCH_CHECK(src.dim() == 4 && src.size(3) == 3, op, ": src must be [N, Hs, Ws, 3] (3 channels last)");
   TORCH_CHECK(src.is_contiguous(), op, ": src must be contiguous");
   const int out_dtype = dtype_code(out);
-  TORCH_CHECK(out.dim() == 4 && out.size(1) == 3 && out.size(0) == src.size(0), op,
+  TORCH_CHECK(out.dim() == 4 && out.size(1) == 3 && (index || out.size(0) == src.size(0)), op,
               ": out must be [N, 3, Ho, Wo] with src's N");
-  const int64_t N = src.size(0), Hs = src.size(1), Ws = src.size(2), Ho = out.size(2), Wo = out.size(3);
+  if (index) {
+    TORCH_CHECK(index->is_cuda() && index->device() == src.device(), op, ": index must be on the store's GPU");
+    TORCH_CHECK(index->scalar_type() == at::kInt && index->dim() == 1 && index->is_contiguous(), op,
+                ": index must be a contiguous int32 [N], got ", index->scalar_type());
+    TORCH_CHECK(index->size(0) == out.size(0), op, ": index has ", index->size(0), " entries, out ", out.size(0),
+                " images");
+    TORCH_CHECK(src.size(0) >= 1 && src.size(0) < (int64_t(1) << 31), op, ": the store must hold 1 <= P < 2^31 images");
+  }
+  const int64_t N = out.size(0), Hs = src.size(1), Ws = src.size(2), Ho = out.size(2), Wo = out.size(3);
   TORCH_CHECK(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, op, ": empty image");
   const int64_t want[4] = {Ho * Wo * 3, 1, Wo * 3, 3};
   for (int d = 0; d < 4; ++d)
@@ -504,15 +513,17 @@ static AugmentDims check_augment_args(const char* op, const at::Tensor& src, con
               op, ": geom must be a contiguous fp32 [N, 4]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(geom.data_ptr()) % 16 == 0, op, ": geom must be 16-byte aligned");
   // a row's two x taps are read by one 8-byte load that is kept inside the tensor
-  TORCH_CHECK(N == 0 || src.numel() >= 9, op, ": src must hold at least three pixels");
+  TORCH_CHECK(N == 0 || (index ? Hs * Ws : src.numel() / 3) >= 3, op,
+              index ? ": an image must hold at least three pixels" : ": src must hold at least three pixels");
   TORCH_CHECK(flip.scalar_type() == at::kByte && flip.dim() == 1 && flip.size(0) == N && flip.is_contiguous(), op,
               ": flip must be a contiguous uint8 [N]");
   for (const at::Tensor* t : {&scale, &bias})
     TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == 3 && t->is_contiguous(), op,
                 ": scale and bias must be contiguous fp32 [3]");
   TORCH_CHECK(pad >= 0 && pad < (1 << 20), op, ": pad must be >= 0, got ", pad);
-  TORCH_CHECK(src.numel() < (int64_t(1) << 31) && out.numel() < (int64_t(1) << 31), op,
-              ": src and out must have fewer than 2^31 elements");
+  TORCH_CHECK((index ? Hs * Ws * 3 : src.numel()) < (int64_t(1) << 31) && out.numel() < (int64_t(1) << 31), op,
+              index ? ": an image and out must have fewer than 2^31 elements"
+                    : ": src and out must have fewer than 2^31 elements");
   return AugmentDims{(int)N, (int)Hs, (int)Ws, (int)Ho, (int)Wo, out_dtype};
 }
 
@@ -524,27 +535,54 @@ void augment_(at::Tensor src, at::Tensor out, at::Tensor geom, at::Tensor flip, 
                  current_stream(out));
 }
 
+// augment_ reading its batch in place from a resident store: image n is store row index[n] (dla_kernels.h). The
+// values of index live on the device and are the caller's to keep in [0, P) (ops/augment.py checks a host index).
+void augment_gather_(at::Tensor store, at::Tensor index, at::Tensor out, at::Tensor geom, at::Tensor flip,
+                     at::Tensor scale, at::Tensor bias, int64_t pad) {
+  const AugmentDims d = check_augment_args("augment_gather_", store, out, geom, flip, scale, bias, pad, &index);
+  launch_augment_gather(store.data_ptr<uint8_t>(), store.size(0), index.data_ptr<int32_t>(), out.data_ptr(), d.dtype,
+                        geom.data_ptr<float>(), flip.data_ptr<uint8_t>(), scale.data_ptr<float>(),
+                        bias.data_ptr<float>(), d.N, d.Hs, d.Ws, d.Ho, d.Wo, (int)pad, current_stream(out));
+}
+
 // augment_ with Mixup / CutMix: per sample a partner image, a weight and a box on the output grid (dla_kernels.h).
 // The values of partner, lam and box live on the device and are the caller's to keep in range (ops/augment.py
 // checks host tensors); blend = false promises lam == 1 everywhere.
+static void check_mix_args(const char* op, const at::Tensor& src, const AugmentDims& d, const at::Tensor& partner,
+                           const at::Tensor& lam, const at::Tensor& box) {
+  for (const at::Tensor* t : {&partner, &lam, &box})
+    TORCH_CHECK(t->is_cuda() && t->device() == src.device(), op, ": partner, lam and box must be on src's GPU");
+  TORCH_CHECK(partner.scalar_type() == at::kInt && partner.dim() == 1 && partner.size(0) == d.N &&
+                  partner.is_contiguous(),
+              op, ": partner must be a contiguous int32 [N]");
+  TORCH_CHECK(lam.scalar_type() == at::kFloat && lam.dim() == 1 && lam.size(0) == d.N && lam.is_contiguous(), op,
+              ": lam must be a contiguous fp32 [N]");
+  TORCH_CHECK(box.scalar_type() == at::kInt && box.dim() == 2 && box.size(0) == d.N && box.size(1) == 4 &&
+                  box.is_contiguous(),
+              op, ": box must be a contiguous int32 [N, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(box.data_ptr()) % 16 == 0, op, ": box must be 16-byte aligned");
+}
+
 void augment_mix_(at::Tensor src, at::Tensor out, at::Tensor geom, at::Tensor flip, at::Tensor partner, at::Tensor lam,
                   at::Tensor box, at::Tensor scale, at::Tensor bias, int64_t pad, bool blend) {
   const AugmentDims d = check_augment_args("augment_mix_", src, out, geom, flip, scale, bias, pad);
-  for (const at::Tensor* t : {&partner, &lam, &box})
-    TORCH_CHECK(t->is_cuda() && t->device() == src.device(), "augment_mix_: partner, lam and box must be on src's GPU");
-  TORCH_CHECK(partner.scalar_type() == at::kInt && partner.dim() == 1 && partner.size(0) == d.N &&
-                  partner.is_contiguous(),
-              "augment_mix_: partner must be a contiguous int32 [N]");
-  TORCH_CHECK(lam.scalar_type() == at::kFloat && lam.dim() == 1 && lam.size(0) == d.N && lam.is_contiguous(),
-              "augment_mix_: lam must be a contiguous fp32 [N]");
-  TORCH_CHECK(box.scalar_type() == at::kInt && box.dim() == 2 && box.size(0) == d.N && box.size(1) == 4 &&
-                  box.is_contiguous(),
-              "augment_mix_: box must be a contiguous int32 [N, 4]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(box.data_ptr()) % 16 == 0, "augment_mix_: box must be 16-byte aligned");
+  check_mix_args("augment_mix_", src, d, partner, lam, box);
   launch_augment_mix(src.data_ptr<uint8_t>(), out.data_ptr(), d.dtype, geom.data_ptr<float>(),
                      flip.data_ptr<uint8_t>(), partner.data_ptr<int32_t>(), lam.data_ptr<float>(),
                      box.data_ptr<int32_t>(), scale.data_ptr<float>(), bias.data_ptr<float>(), d.N, d.Hs, d.Ws, d.Ho,
                      d.Wo, (int)pad, blend, current_stream(out));
+}
+
+// augment_mix_ over a resident store: partner[n] is a position in the batch, whose image is row index[partner[n]].
+void augment_mix_gather_(at::Tensor store, at::Tensor index, at::Tensor out, at::Tensor geom, at::Tensor flip,
+                         at::Tensor partner, at::Tensor lam, at::Tensor box, at::Tensor scale, at::Tensor bias,
+                         int64_t pad, bool blend) {
+  const AugmentDims d = check_augment_args("augment_mix_gather_", store, out, geom, flip, scale, bias, pad, &index);
+  check_mix_args("augment_mix_gather_", store, d, partner, lam, box);
+  launch_augment_mix_gather(store.data_ptr<uint8_t>(), store.size(0), index.data_ptr<int32_t>(), out.data_ptr(),
+                            d.dtype, geom.data_ptr<float>(), flip.data_ptr<uint8_t>(), partner.data_ptr<int32_t>(),
+                            lam.data_ptr<float>(), box.data_ptr<int32_t>(), scale.data_ptr<float>(),
+                            bias.data_ptr<float>(), d.N, d.Hs, d.Ws, d.Ho, d.Wo, (int)pad, blend, current_stream(out));
 }
 
 std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor target) {
@@ -708,6 +746,15 @@ void bind_ops(pybind11::module& m) {
         pybind11::arg("src"), pybind11::arg("out"), pybind11::arg("geom"), pybind11::arg("flip"),
         pybind11::arg("partner"), pybind11::arg("lam"), pybind11::arg("box"), pybind11::arg("scale"),
         pybind11::arg("bias"), pybind11::arg("pad") = 0, pybind11::arg("blend") = true);
+  m.def("augment_gather_", &augment_gather_,
+        "augment_ reading image n in place from row index[n] of a resident uint8 store [P,Hs,Ws,3] of any size",
+        pybind11::arg("store"), pybind11::arg("index"), pybind11::arg("out"), pybind11::arg("geom"),
+        pybind11::arg("flip"), pybind11::arg("scale"), pybind11::arg("bias"), pybind11::arg("pad") = 0);
+  m.def("augment_mix_gather_", &augment_mix_gather_,
+        "augment_mix_ over a resident store: image n is row index[n], its partner row index[partner[n]]",
+        pybind11::arg("store"), pybind11::arg("index"), pybind11::arg("out"), pybind11::arg("geom"),
+        pybind11::arg("flip"), pybind11::arg("partner"), pybind11::arg("lam"), pybind11::arg("box"),
+        pybind11::arg("scale"), pybind11::arg("bias"), pybind11::arg("pad") = 0, pybind11::arg("blend") = true);
   m.def("xent_fwd", &xent_fwd, "fused log-softmax + NLL forward");
   m.def("xent_bwd", &xent_bwd, "fused log-softmax + NLL backward");
   m.def("xent_metrics_fwd", &xent_metrics_fwd,

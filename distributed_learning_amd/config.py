@@ -88,6 +88,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "in [0, 1) (0 = off); every evaluation then also reports the averaged model (eval_ema)")
     p.add_argument("--ema_warmup", type=int, default=0, choices=[0, 1],
                    help="1 = the decay of update t is min(ema_decay, (1 + t) / (10 + t))")
+    p.add_argument("--staged_dir", default=None,
+                   help="ImageNet models: read the uint8 256x256 staging images from the files that "
+                        "`python -m distributed_learning_amd.stage` wrote here instead of decoding the JPEG tree "
+                        "(needs --augment standard, which takes the raw uint8 form)")
+    p.add_argument("--resident", type=int, default=0, choices=[0, 1],
+                   help="1 = hold the rank's data shard in device memory for the whole run and let the augmentation "
+                        "kernel read each batch in place by index: no decode, collate or image copy per step (needs "
+                        "--augment standard); a shard that does not fit beside the step is an error")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--master_port", type=int, default=29501)
     # MI355X options
@@ -146,6 +154,16 @@ def parse_args(argv: Optional[List[str]] = None):
         parser.error("--ema_decay must be in [0, 1)")
     if (config.mixup_alpha > 0 or config.cutmix_alpha > 0) and config.augment == "none":
         parser.error("--mixup_alpha / --cutmix_alpha need --augment standard: the mixing lives in that kernel")
+    if config.resident and config.augment == "none":
+        parser.error("--resident 1 needs --augment standard: the resident store is read by that kernel")
+    if config.staged_dir and config.augment == "none":
+        parser.error("--staged_dir needs --augment standard: the staged files hold the raw uint8 form")
+    if config.staged_dir:
+        from .models import MODELS
+
+        spec = MODELS.get(config.model or config.model_type)
+        if spec is not None and spec.dataset != "imagenet":
+            parser.error(f"--staged_dir needs an ImageNet model: {spec.dataset} has no staged form")
     if config.augment != "none":
         from .models import MODELS
 

@@ -202,10 +202,58 @@ class ImageFolder(torch.utils.data.Dataset):
         return (x - self.mean) / self.std, label
 
 
-def load_dataset(kind: str, root: str, train: bool = True, raw: bool = False):
+class StagedImages(torch.utils.data.Dataset):
+    """The files ``python -m distributed_learning_amd.stage`` writes, as a dataset: ``ImageFolder(raw=True)``'s
+    items ``(uint8 [256, 256, 3], label)`` and ``.classes`` without the JPEG tree or a decode. ``.images`` is the
+    memory-mapped uint8 ``[N, 256, 256, 3]`` array and ``.labels`` int64 ``[N]`` (:class:`ResidentStore`'s bulk
+    fill slices them). The arrays are checked against ``{split}_meta.json``; a mismatch raises."""
+
+    def __init__(self, directory: str, split: str = "train"):
+        import json
+
+        d = Path(directory)
+        with open(d / f"{split}_meta.json") as f:
+            self.meta = json.load(f)
+        self._path, self._images = str(d / f"{split}_images.npy"), None
+        self.labels = np.load(d / f"{split}_labels.npy")
+        self.classes = list(self.meta["classes"])
+        n, stage = int(self.meta["count"]), int(self.meta["stage"])
+        if self.images.dtype != np.uint8 or tuple(self.images.shape) != (n, stage, stage, 3):
+            raise ValueError(f"{d}/{split}_images.npy is {self.images.dtype} {tuple(self.images.shape)}, but "
+                             f"{split}_meta.json describes uint8 {(n, stage, stage, 3)}")
+        if self.labels.dtype != np.int64 or tuple(self.labels.shape) != (n,):
+            raise ValueError(f"{d}/{split}_labels.npy is {self.labels.dtype} {tuple(self.labels.shape)}, but "
+                             f"{split}_meta.json describes int64 {(n,)}")
+        if n and not (0 <= int(self.labels.min()) and int(self.labels.max()) < len(self.classes)):
+            raise ValueError(f"{d}/{split}_labels.npy holds labels outside the {len(self.classes)} classes")
+
+    @property
+    def images(self) -> np.ndarray:
+        if self._images is None:
+            self._images = np.load(self._path, mmap_mode="r")
+        return self._images
+
+    def __getstate__(self):
+        # a loader worker maps the file itself: pickling a memory map would copy the whole array
+        return dict(self.__dict__, _images=None)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __getitem__(self, i):
+        return torch.from_numpy(np.array(self.images[i])), int(self.labels[i])
+
+
+def load_dataset(kind: str, root: str, train: bool = True, raw: bool = False, staged_dir: Optional[str] = None):
     """The training split, or with ``train=False`` the held-out one: MNIST ``t10k``, CIFAR-10
     ``test_batch.bin``, ImageNet ``root/ImageFolderVal``. ``raw``: uint8 HWC images for the device-side
-    transform (CIFAR-10 and ImageNet; MNIST has no raw form)."""
+    transform (CIFAR-10 and ImageNet; MNIST has no raw form). ``staged_dir`` (ImageNet, raw): the staged files of
+    ``distributed_learning_amd.stage`` instead of the JPEG tree, which is then not needed."""
+    if staged_dir:
+        if kind != "imagenet" or not raw:
+            raise ValueError("staged_dir holds raw (uint8 HWC) ImageNet staging images: it needs kind 'imagenet' "
+                             "and raw=True")
+        return StagedImages(staged_dir, "train" if train else "val")
     if kind == "mnist":
         if raw:
             raise ValueError("MNIST has no raw (uint8 HWC) form: the device-side augmentation serves the "
@@ -273,6 +321,189 @@ class EvalPartition:
 def get_eval_loader(dataset, rank: int, world: int, batch_size: int = PER_WORKER_BATCH_SIZE,
                     num_workers: int = 0) -> EvalPartition:
     return EvalPartition(dataset, rank, world, batch_size, num_workers)
+
+
+# ------------------------------------------------------------------------------------------------
+# Device-resident shards (--resident 1): the augmentation kernel reads its samples in place, by index
+# ------------------------------------------------------------------------------------------------
+def _bulk_images(dataset):
+    """The dataset's images as one uint8 ``[n, Hs, Ws, 3]`` array when it exposes one (``TensorDataset.x`` of
+    ``load_cifar10(raw=True)``, ``StagedImages.images``), with its labels; else ``(None, None)``."""
+    for images, labels in ((getattr(dataset, "images", None), getattr(dataset, "labels", None)),
+                           (getattr(dataset, "x", None), getattr(dataset, "y", None))):
+        if images is not None and labels is not None and len(images.shape) == 4 and images.shape[3] == 3 \
+                and str(images.dtype).endswith("uint8"):
+            return images, labels
+    return None, None
+
+
+class ResidentStore:
+    """A rank's data shard held on its training device for the whole run: ``images`` uint8 ``[P + 1, Hs, Ws, 3]``
+    and, on the host, ``labels`` int64 ``[P + 1]``. Row ``P`` is the padding sample of an evaluation -- a zero
+    image with label :attr:`EvalPartition.IGNORE`. ``ops.augment.augment(store.images, ..., index=)`` reads a
+    batch's rows in place: after the fill there is no decode, no collate and no host-to-device image copy.
+
+    ``images`` (uint8 ``[P, Hs, Ws, 3]``, a tensor or a numpy array, memory-mapped or not) is copied in chunks of at
+    most :attr:`CHUNK_BYTES`; :meth:`from_dataset` fills from any dataset and an index list. On a GPU a store
+    larger than ``max_fraction`` of the memory free at construction is refused: the shard either fits beside the
+    step or the run stops -- there is no fallback to host memory. The 0.5 is a policy default, not a measurement;
+    it keeps a store from silently crowding out the step."""
+
+    CHUNK_BYTES = 256 << 20
+
+    def __init__(self, images, labels, device, max_fraction: float = 0.5):
+        shape = tuple(int(v) for v in images.shape)
+        if len(shape) != 4 or shape[3] != 3 or not str(images.dtype).endswith("uint8"):
+            raise ValueError(f"ResidentStore: images must be uint8 [P, Hs, Ws, 3], got {images.dtype} {shape}")
+        labels = torch.as_tensor(np.asarray(labels)).to(torch.int64).reshape(-1)
+        if labels.shape[0] != shape[0]:
+            raise ValueError(f"ResidentStore: {shape[0]} images but {labels.shape[0]} labels")
+        self._allocate(shape[0], shape[1:3], device, max_fraction)
+        self._fill(lambda lo, hi: (torch.as_tensor(np.ascontiguousarray(images[lo:hi])), labels[lo:hi]))
+
+    @classmethod
+    def from_dataset(cls, dataset, index: Sequence[int], device, max_fraction: float = 0.5) -> "ResidentStore":
+        """Row ``i`` is ``dataset[index[i]]`` (items ``(uint8 [Hs, Ws, 3], label)``). A dataset that exposes its
+        images as one array is sliced in bulk; any other is read item by item, once."""
+        index = [int(i) for i in index]
+        images, labels = _bulk_images(dataset)
+        self = cls.__new__(cls)
+        if images is not None:
+            hw = tuple(images.shape[1:3])
+            labels = torch.as_tensor(np.asarray(labels)).to(torch.int64)
+
+            def chunk(lo, hi):
+                rows = np.asarray(index[lo:hi], dtype=np.int64)
+                block = images[torch.from_numpy(rows)] if torch.is_tensor(images) else images[rows]
+                return torch.as_tensor(np.ascontiguousarray(block)), labels[torch.from_numpy(rows)]
+        else:
+            if len(dataset) == 0:
+                raise ValueError("ResidentStore: empty dataset")
+            hw = tuple(torch.as_tensor(dataset[index[0] if index else 0][0]).shape[:2])
+
+            def chunk(lo, hi):
+                items = [dataset[i] for i in index[lo:hi]]
+                return (torch.stack([torch.as_tensor(x) for x, _ in items]),
+                        torch.tensor([int(y) for _, y in items], dtype=torch.int64))
+        self._allocate(len(index), hw, device, max_fraction)
+        self._fill(chunk)
+        return self
+
+    @staticmethod
+    def check_fits(nbytes: int, device, max_fraction: float) -> None:
+        device = torch.device(device)
+        if device.type != "cuda":
+            return
+        free, total = torch.cuda.mem_get_info(device)
+        if nbytes > max_fraction * free:
+            raise RuntimeError(
+                f"resident store of {nbytes} bytes exceeds {max_fraction} of the {free} bytes free on {device} "
+                f"({total} in all): the shard does not fit beside the training step. Use more ranks (a rank holds "
+                f"1/world of the set) or run without --resident 1; there is no host-memory fallback")
+
+    def _allocate(self, rows: int, hw, device, max_fraction: float) -> None:
+        self.device = torch.device(device)
+        self.rows, self.hw = int(rows), (int(hw[0]), int(hw[1]))
+        self.check_fits((self.rows + 1) * self.hw[0] * self.hw[1] * 3, self.device, max_fraction)
+        self.images = torch.empty((self.rows + 1,) + self.hw + (3,), dtype=torch.uint8, device=self.device)
+        self.images[self.rows].zero_()
+        self.labels = torch.full((self.rows + 1,), EvalPartition.IGNORE, dtype=torch.int64)
+
+    def _fill(self, chunk) -> None:
+        """``chunk(lo, hi) -> (uint8 [hi - lo, Hs, Ws, 3], int64 [hi - lo])`` on the host, at most CHUNK_BYTES each."""
+        step = max(1, self.CHUNK_BYTES // (self.hw[0] * self.hw[1] * 3))
+        for lo in range(0, self.rows, step):
+            hi = min(lo + step, self.rows)
+            x, y = chunk(lo, hi)
+            if tuple(x.shape) != (hi - lo,) + self.hw + (3,) or x.dtype != torch.uint8:
+                raise ValueError(f"ResidentStore: rows {lo}..{hi} are {x.dtype} {tuple(x.shape)}, expected uint8 "
+                                 f"{(hi - lo,) + self.hw + (3,)}")
+            self.images[lo:hi].copy_(x)
+            self.labels[lo:hi] = y
+
+    def __len__(self) -> int:
+        return self.rows
+
+    @property
+    def nbytes(self) -> int:
+        return self.images.numel()
+
+
+class ResidentBatches:
+    """The training iterator over a :class:`ResidentStore`, in the exact order of :func:`get_partition_loader`'s
+    loader: it owns an ``EpochSampler(P, seed)`` (``.epoch_sampler``, driven by the training loop's ``set_epoch``
+    the same way) and one iteration walks ``order(epoch)[start:]`` in consecutive chunks of ``batch_size``, a short
+    tail dropped. It yields ``(index int32 [B], y int64 [B])`` on the host: batch ``k`` of a run names the samples
+    the ``DataLoader`` path would have loaded, in the same order, resume offsets included."""
+
+    def __init__(self, store: ResidentStore, batch_size: int, seed: int = 1234):
+        self.store, self.batch_size = store, int(batch_size)
+        self.epoch_sampler = EpochSampler(len(store), seed)
+
+    def __len__(self) -> int:
+        return len(self.store) // self.batch_size
+
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        order = torch.tensor(list(self.epoch_sampler), dtype=torch.int64)
+        b = self.batch_size
+        for lo in range(0, len(order) - b + 1, b):
+            rows = order[lo:lo + b]
+            yield rows.to(torch.int32), self.store.labels[rows]
+
+
+def get_resident_batches(dataset, node_id: int, worker_id: int, node_dev: int, total_dev: int,
+                         batch_size: int = PER_WORKER_BATCH_SIZE, device="cpu", seed: int = 1234,
+                         max_fraction: float = 0.5) -> ResidentBatches:
+    """:func:`get_partition_loader` with the rank's partition held on ``device``: the same partition, the same
+    sampler seed, so the same samples in every batch."""
+    stream = node_id * node_dev + worker_id
+    part = DataPartitioner(dataset, total_dev, batch_size, seed).use(stream)
+    store = ResidentStore.from_dataset(dataset, part.index.tolist(), device, max_fraction)
+    return ResidentBatches(store, batch_size, seed + stream)
+
+
+class ResidentEval:
+    """:class:`EvalPartition`'s rule over a :class:`ResidentStore`: rank ``r`` of ``W`` takes samples ``r, r + W,
+    ...`` of the held-out set, every rank runs the batch count of the largest share, and what a rank lacks is
+    index ``P`` -- the store's zero row, target ``IGNORE``. Yields ``(index int32 [B], y int64 [B])`` on the host.
+
+    ``total``: the size of the whole held-out set when ``store`` holds this rank's share only, in that order
+    (:meth:`from_dataset`); without it the store holds the whole set and the rank indexes its share."""
+
+    IGNORE = EvalPartition.IGNORE
+
+    def __init__(self, store: ResidentStore, rank: int, world: int, batch_size: int, total: Optional[int] = None):
+        if not 0 <= rank < world:
+            raise ValueError(f"rank {rank} outside a world of {world}")
+        self.store, self.batch_size = store, int(batch_size)
+        p = len(store)
+        if total is None:
+            total, share = p, list(range(rank, p, world))
+        else:
+            share = list(range(p))
+            if p != len(range(rank, int(total), world)):
+                raise ValueError(f"ResidentEval: a store of {p} rows is not rank {rank}'s share of {total} samples "
+                                 f"over {world} ranks")
+        largest = (int(total) + world - 1) // world
+        self.batches = (largest + self.batch_size - 1) // self.batch_size
+        self.index = torch.full((self.batches * self.batch_size,), p, dtype=torch.int64)
+        self.index[:len(share)] = torch.tensor(share, dtype=torch.int64)
+
+    @classmethod
+    def from_dataset(cls, dataset, rank: int, world: int, batch_size: int, device,
+                     max_fraction: float = 0.5) -> "ResidentEval":
+        """Holds only the rank's share ``dataset[r], dataset[r + W], ...``."""
+        store = ResidentStore.from_dataset(dataset, range(rank, len(dataset), world), device, max_fraction)
+        return cls(store, rank, world, batch_size, total=len(dataset))
+
+    def __len__(self) -> int:
+        return self.batches
+
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        b = self.batch_size
+        for k in range(self.batches):
+            rows = self.index[k * b:(k + 1) * b]
+            yield rows.to(torch.int32), self.store.labels[rows]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -25,11 +25,16 @@ The crop boxes and flips of a batch come from :class:`AugmentParams`, a pure fun
 :func:`augment_mix` is the same pass with Mixup / CutMix: every sample is combined with a partner image that is
 sampled with its own geometry (mixed instantiations of the same kernel); :class:`MixParams` draws its per-batch
 parameters, again as a pure function of ``(seed, stream, step)``.
+
+Both take ``index=``: ``src`` is then a resident store ``[P, Hs, Ws, 3]`` of any size (a rank's whole data shard in
+HBM, :class:`~distributed_learning_amd.data.ResidentStore`) and batch image ``n`` is store row ``index[n]``, read
+in place by indexed instantiations of the same kernel -- no gathered batch is ever written. The result is, bit
+for bit, the un-indexed call on ``src[index]``.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -68,7 +73,8 @@ def _elements_ok(n: int, what: str) -> None:
                                f"lower the per-GPU batch")
 
 
-def _check(src, geom, flip, out_hw, dtype, pad) -> None:
+def _check(src, geom, flip, out_hw, dtype, pad, index=None) -> int:
+    """Returns the batch size: ``src``'s, or with ``index`` (``src`` is a store) the index's length."""
     if src.dtype != torch.uint8:
         raise TypeError(f"augment: src must be uint8, got {src.dtype}")
     if src.dim() != 4 or src.shape[3] != 3:
@@ -76,6 +82,14 @@ def _check(src, geom, flip, out_hw, dtype, pad) -> None:
     if not src.is_contiguous():
         raise ValueError("augment: src must be contiguous")
     n = src.shape[0]
+    if index is not None:
+        if index.dtype != torch.int32 or index.dim() != 1:
+            raise ValueError(f"augment: index must be int32 [N], got {index.dtype} {tuple(index.shape)}")
+        rows, n = n, index.shape[0]
+        if rows < 1:
+            raise ValueError("augment: an indexed store must hold at least one image")
+        if index.device.type == "cpu" and n and not bool(((index >= 0) & (index < rows)).all()):
+            raise ValueError(f"augment: index must be in [0, {rows})")
     if tuple(geom.shape) != (n, 4) or geom.dtype != torch.float32:
         raise ValueError(f"augment: geom must be fp32 [{n}, 4], got {geom.dtype} {tuple(geom.shape)}")
     if tuple(flip.shape) != (n,) or flip.dtype != torch.uint8:
@@ -86,28 +100,39 @@ def _check(src, geom, flip, out_hw, dtype, pad) -> None:
         raise ValueError(f"augment: bad sizes {tuple(src.shape)} -> {tuple(out_hw)}")
     if int(pad) < 0:
         raise ValueError(f"augment: pad must be >= 0, got {pad}")
-    _elements_ok(src.numel(), "augment src")
+    # an indexed store is addressed per image (64-bit base, 32-bit offsets inside): only one image is limited
+    _elements_ok(src[0].numel() if index is not None else src.numel(), "augment src")
     _elements_ok(n * 3 * out_hw[0] * out_hw[1], "augment out")
+    return n
 
 
 def augment(src_u8: torch.Tensor, geom: torch.Tensor, flip: torch.Tensor, mean: Sequence[float],
-            std: Sequence[float], out_hw: Tuple[int, int], dtype: torch.dtype, pad: int = 0) -> torch.Tensor:
+            std: Sequence[float], out_hw: Tuple[int, int], dtype: torch.dtype, pad: int = 0,
+            index: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``src_u8`` uint8 ``[N, Hs, Ws, 3]`` -> ``dtype`` ``[N, 3, Ho, Wo]`` in channels-last memory.
+
+    ``index`` int32 ``[N]``: ``src_u8`` is a store ``[P, Hs, Ws, 3]`` and image ``n`` is its row ``index[n]``, read
+    in place. A host index is range-checked and copied to the device; a device index is the caller's to keep in
+    ``[0, P)``.
 
     ``geom`` fp32 ``[N, 4]`` and ``flip`` uint8 ``[N]`` may live on the host (:meth:`AugmentParams.params`); they
     are copied to ``src_u8``'s device. On a GPU this is the native kernel (a missing extension is an error);
     on the CPU a torch implementation of the same definition."""
     out_hw = (int(out_hw[0]), int(out_hw[1]))
-    _check(src_u8, geom, flip, out_hw, dtype, pad)
+    n = _check(src_u8, geom, flip, out_hw, dtype, pad, index)
     dev = src_u8.device
     geom, flip = geom.to(dev, non_blocking=True).contiguous(), flip.to(dev, non_blocking=True).contiguous()
     scale, bias = _coefficients(mean, std, dev)
-    n = src_u8.shape[0]
     if dev.type != "cuda":
+        if index is not None:
+            src_u8 = src_u8[index.to(dev).long()]
         return _augment_torch(src_u8, geom, flip, scale, bias, out_hw, dtype, int(pad))
     C = _ext.require()
     out = torch.empty((n, out_hw[0], out_hw[1], 3), device=dev, dtype=dtype).permute(0, 3, 1, 2)
-    C.augment_(src_u8, out, geom, flip, scale, bias, int(pad))
+    if index is not None:
+        C.augment_gather_(src_u8, index.to(dev, non_blocking=True).contiguous(), out, geom, flip, scale, bias, int(pad))
+    else:
+        C.augment_(src_u8, out, geom, flip, scale, bias, int(pad))
     return out
 
 
@@ -137,7 +162,8 @@ def _check_mix(n: int, partner, lam, box, out_hw, blend: bool) -> None:
 
 def augment_mix(src_u8: torch.Tensor, geom: torch.Tensor, flip: torch.Tensor, partner: torch.Tensor,
                 lam: torch.Tensor, box: torch.Tensor, mean: Sequence[float], std: Sequence[float],
-                out_hw: Tuple[int, int], dtype: torch.dtype, pad: int = 0, blend: bool = True) -> torch.Tensor:
+                out_hw: Tuple[int, int], dtype: torch.dtype, pad: int = 0, blend: bool = True,
+                index: Optional[torch.Tensor] = None) -> torch.Tensor:
     """:func:`augment` with Mixup / CutMix in the same pass. With ``A(j)`` the fp32 value :func:`augment` gives
     for source image ``j`` with ``geom[j]`` and ``flip[j]``, ``p = partner[n]`` and ``box[n] = (y0, x0, y1, x1)``
     on the output grid (independent of either image's flip)::
@@ -148,20 +174,28 @@ def augment_mix(src_u8: torch.Tensor, geom: torch.Tensor, flip: torch.Tensor, pa
     Mixup is an empty box with ``0 < lam < 1``, CutMix ``lam = 1`` with a box. ``partner`` int32 ``[N]``, ``lam``
     fp32 ``[N]`` and ``box`` int32 ``[N, 4]`` may live on the host (:meth:`MixParams.params`), where their values
     are range-checked; a device tensor's values are the caller's to keep in range. ``blend=False`` is the select
-    form -- one sample per pixel, from ``n`` or ``p`` -- and needs ``lam == 1`` for every sample."""
+    form -- one sample per pixel, from ``n`` or ``p`` -- and needs ``lam == 1`` for every sample.
+
+    ``index``: as in :func:`augment`; ``partner`` stays a position in the batch, so the partner of ``n`` is store
+    row ``index[partner[n]]`` with ``geom[partner[n]]`` and ``flip[partner[n]]``."""
     out_hw = (int(out_hw[0]), int(out_hw[1]))
-    _check(src_u8, geom, flip, out_hw, dtype, pad)
-    n = src_u8.shape[0]
+    n = _check(src_u8, geom, flip, out_hw, dtype, pad, index)
     _check_mix(n, partner, lam, box, out_hw, bool(blend))
     dev = src_u8.device
     geom, flip = geom.to(dev, non_blocking=True).contiguous(), flip.to(dev, non_blocking=True).contiguous()
     partner, lam, box = (t.to(dev, non_blocking=True).contiguous() for t in (partner, lam, box))
     scale, bias = _coefficients(mean, std, dev)
     if dev.type != "cuda":
+        if index is not None:
+            src_u8 = src_u8[index.to(dev).long()]
         return _augment_mix_torch(src_u8, geom, flip, partner, lam, box, scale, bias, out_hw, dtype, int(pad))
     C = _ext.require()
     out = torch.empty((n, out_hw[0], out_hw[1], 3), device=dev, dtype=dtype).permute(0, 3, 1, 2)
-    C.augment_mix_(src_u8, out, geom, flip, partner, lam, box, scale, bias, int(pad), bool(blend))
+    if index is not None:
+        C.augment_mix_gather_(src_u8, index.to(dev, non_blocking=True).contiguous(), out, geom, flip, partner, lam,
+                              box, scale, bias, int(pad), bool(blend))
+    else:
+        C.augment_mix_(src_u8, out, geom, flip, partner, lam, box, scale, bias, int(pad), bool(blend))
     return out
 
 

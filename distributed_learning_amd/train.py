@@ -27,6 +27,11 @@ Differences by design:
 * optional weight averaging (``--ema_decay``, ``--ema_warmup``): the optimizer's update kernels also advance an
   exponential moving average of every weight (ops/optim.py ``ModelEMA``), every evaluation runs a second time
   from the averages (``eval_ema`` lines), and checkpoints carry them; without the flag nothing of it runs;
+* optional staged and device-resident data (``--staged_dir``, ``--resident 1``, both on top of ``--augment
+  standard``): the ImageNet staging images come from the files of ``distributed_learning_amd.stage`` instead of a
+  per-epoch JPEG decode, and with ``--resident 1`` the rank's shard lives on the device (``data.ResidentStore``),
+  ``get_data`` yields an index list in the loader's exact order and ``data2dev`` is the indexed form of the
+  augmentation kernel reading its samples in place; without the flags nothing of it runs;
 * on GPU the step is the framework's measured headline path (the one ``bench.py`` times): native
   MFMA convolutions / FC heads and fused BN kernels, bf16 weights with fp32 master weights in the
   fused SGD (``--precision bf16``, default), on-device synthetic batches, and every gradient
@@ -93,19 +98,36 @@ def setup_compute_path(config, device) -> str:
     return prec
 
 
+def _no_dataset(config) -> bool:
+    """Synthetic input: asked for, or no dataset to read (a staged directory stands in for the dataset root)."""
+    if config.random_input:
+        return True
+    if getattr(config, "staged_dir", None):
+        return False
+    return not config.dataset_root or not os.path.isdir(config.dataset_root)
+
+
 def _data_for(config, spec, device, rank: int, node_id: int, worker_id: int, dtype=torch.float32):
-    if config.random_input or not config.dataset_root or not os.path.isdir(config.dataset_root):
+    if _no_dataset(config):
         if not config.random_input:
             print_d(f"dataset root {config.dataset_root!r} not found: using synthetic data", Level.WARNING)
         return D.SyntheticBatches(config.batch_size, spec.input_shape, spec.num_classes, device,
                                   dtype=dtype, seed=config.seed, rank=rank,
                                   channels_last=_channels_last(config, device))
-    ds = D.load_dataset(spec.dataset, config.dataset_root, raw=_augmenting(config))
+    ds = D.load_dataset(spec.dataset, config.dataset_root, raw=_augmenting(config),
+                        staged_dir=getattr(config, "staged_dir", None))
+    if _resident(config):
+        return D.get_resident_batches(ds, node_id, worker_id, config.node_dev, config.total_dev, config.batch_size,
+                                      device)
     return D.get_partition_loader(ds, node_id, worker_id, config.node_dev, config.total_dev, config.batch_size)
 
 
 def _augmenting(config) -> bool:
     return getattr(config, "augment", "none") != "none"
+
+
+def _resident(config) -> bool:
+    return bool(getattr(config, "resident", 0))
 
 
 def _mixing(config) -> bool:
@@ -116,7 +138,8 @@ def _augmenters(config, spec, device, prec: str, stream: int):
     """``--augment standard``: the (training, evaluation) transforms ``(raw uint8 batch on the device, batch
     number) -> model input`` in the step's dtype and layout, through ops/augment.py: random-resized crop 256 -> 224
     plus flip (ImageNet models) or pad-4 random crop plus flip (CIFAR models) for training, the centre crop for
-    evaluation. The training parameters are a function of (seed, partition ``stream``, batch number) alone."""
+    evaluation. The training parameters are a function of (seed, partition ``stream``, batch number) alone.
+    ``index=`` (``--resident 1``): ``x`` is a resident store's images and the batch its rows ``index``."""
     if spec.dataset == "imagenet":
         kind, src_hw, pad = "rrc", (D.ImageFolder.STAGE, D.ImageFolder.STAGE), 0
         mean, std = aug.IMAGENET_MEAN, aug.IMAGENET_STD
@@ -133,18 +156,25 @@ def _augmenters(config, spec, device, prec: str, stream: int):
         p = aug.AugmentParams(kind, src_hw, out_hw, seed=config.seed, stream=stream,
                               scale_min=getattr(config, "aug_scale_min", 0.08), pad=pad)
 
-        def apply(x, batch: int, mix=None):
+        def apply(x, batch: int, mix=None, index=None):
             """``mix``: ``(partner, lam, box, blend)`` of :class:`~.ops.augment.MixParams` -- Mixup / CutMix in
             the same kernel pass."""
+            n = x.shape[0] if index is None else index.shape[0]
             if mix is None:
-                x = aug.augment(x, *p.params(batch, x.shape[0]), mean, std, out_hw, dtype, pad)
+                x = aug.augment(x, *p.params(batch, n), mean, std, out_hw, dtype, pad, index=index)
             else:
-                x = aug.augment_mix(x, *p.params(batch, x.shape[0]), *mix[:3], mean, std, out_hw, dtype, pad, mix[3])
+                x = aug.augment_mix(x, *p.params(batch, n), *mix[:3], mean, std, out_hw, dtype, pad, mix[3],
+                                    index=index)
             return x if cl else x.contiguous()  # the fp32 reference-precision path runs NCHW
 
         return apply
 
     return make(kind, pad), make("center", 0)
+
+
+def _indexed(apply: Callable, store) -> Callable:
+    """``apply`` over a resident store: the batch it is handed is the int32 row index."""
+    return lambda index, batch, mix=None: apply(store.images, batch, mix, index=index)
 
 
 def _config_text(config) -> str:
@@ -160,17 +190,24 @@ def _config_text(config) -> str:
     if not getattr(config, "ema_decay", 0.0) > 0:
         for k in ("ema_decay", "ema_warmup"):
             shown.__dict__.pop(k, None)
+    for k in ("staged_dir", "resident"):
+        if not getattr(config, k, None):
+            shown.__dict__.pop(k, None)
     return str(shown)
 
 
 def _eval_data_for(config, spec, device, rank: int, node_id: int, worker_id: int, dtype=torch.float32):
     """Held-out batches of ``--eval_batches``: a synthetic stream of its own (rewound before every evaluation,
     so each one sees the same batches), or this rank's share of the dataset's test split."""
-    if config.random_input or not config.dataset_root or not os.path.isdir(config.dataset_root):
+    if _no_dataset(config):
         return D.SyntheticBatches(config.batch_size, spec.input_shape, spec.num_classes, device,
                                   dtype=dtype, seed=config.seed + 104729, rank=rank,
                                   channels_last=_channels_last(config, device))
-    ds = D.load_dataset(spec.dataset, config.dataset_root, train=False, raw=_augmenting(config))
+    ds = D.load_dataset(spec.dataset, config.dataset_root, train=False, raw=_augmenting(config),
+                        staged_dir=getattr(config, "staged_dir", None))
+    if _resident(config):
+        return D.ResidentEval.from_dataset(ds, node_id * config.node_dev + worker_id, config.total_dev,
+                                           config.batch_size, device)
     return D.get_eval_loader(ds, node_id * config.node_dev + worker_id, config.total_dev, config.batch_size,
                              num_workers=2 if spec.dataset == "imagenet" else 0)
 
@@ -351,6 +388,14 @@ def worker_process(config, distribute_model: Callable, reducer, experiment_name:
             train_aug = None
         if isinstance(eval_set, D.SyntheticBatches):
             eval_aug = None
+    if _resident(config):
+        if isinstance(train_set, D.SyntheticBatches):
+            print_d("--resident 1 ignored: synthetic input is generated on the device already", Level.WARNING)
+        # a resident batch is an index list: the transforms read the store's rows in place
+        if isinstance(train_set, D.ResidentBatches):
+            train_aug = _indexed(train_aug, train_set.store)
+        if isinstance(eval_set, D.ResidentEval):
+            eval_aug = _indexed(eval_aug, eval_set.store)
     train_mix = None  # --mixup_alpha / --cutmix_alpha: per-batch partners, weights and boxes for train_aug and the loss
     if _mixing(config):
         if train_aug is None:
