@@ -12,8 +12,8 @@
 namespace dla {
 
 // ---- multi-tensor (multi_tensor.hip) --------------------------------------------------------
-// The entry and by-value list structs (SgdEntry, PackEntry, EmaEntry, SgdList, PackList, EmaList, EmaSlots,
-// LarsList) and the chunk size are in dla_lists.h.
+// The entry and by-value list structs (SgdEntry, PackEntry, EmaEntry, AdamEntry, SgdList, PackList, EmaList,
+// AdamList, EmaSlots, LarsList) and the chunk size are in dla_lists.h.
 struct SgdParams {
   float lr;
   float momentum;
@@ -67,6 +67,47 @@ void launch_lars_list(const LarsList& list, int nblocks, int grad_dtype, const L
                       hipStream_t stream);
 void launch_lars_ema_list(const LarsList& list, const EmaSlots& ema, const float* omd, int nblocks, int grad_dtype,
                           const LarsTensor* table, const float* ws, hipStream_t stream);
+
+// Fused LAMB (You et al. 2019) and AdamW (multi_tensor.hip), per tensor t with k = step_t + 1:
+//   gh = c g;  m = b1 m + (1 - b1) gh;  v = b2 v + (1 - b2) gh^2
+//   u  = (m / bc1) / (sqrt(v / bc2) + eps) + wd_t p,   bc = 1 - beta^k = -expm1f(k * ln_beta)
+//   p -= alpha_t u,   alpha_t = lr_dev[group_t] * trust_t,   trust_t = ||p|| / ||u|| (LAMB, adapted) or 1
+// LAMB: moments (writes m, v and the per-block (sum p^2, sum u^2), reads step + 1) -> finalize (norms, trust,
+// alpha, bc, commits step + 1) -> apply (recomputes u from p, m, v; reads no gradient). AdamW: finalize ->
+// one update pass. c = grad_scale, or with clipping ws_clip[0] from a gradient square-sum pass before
+// (launch_sqsum_list with a null param, into a LARS-layout workspace).
+// Static per-tensor row of the device table.
+struct AdamTensor {
+  int32_t part_begin, part_end;  // this tensor's range of per-block partials
+  int32_t group;                 // index into lr_dev
+  int32_t adapt;                 // 0: trust 1 (AdamW, or excluded from layer-wise scaling)
+  float weight_decay;            // wd_t: already 0 for an excluded tensor
+  float eps;
+  float beta1, beta2;
+  float omb1, omb2;              // 1 - beta, rounded to fp32 from the host's double
+  float ln_beta1, ln_beta2;      // ln(beta), likewise
+  int32_t* step;                 // the tensor's update count (one int32 in device memory)
+};
+static_assert(sizeof(AdamTensor) == 56, "AdamTensor layout");
+// fp32 workspace: alpha[T] | (bc1, bc2)[T] | (||p_t||, ||u_t||)[T] | partials (sum p^2, sum u^2)[nblocks], 8-byte
+// aligned
+constexpr int64_t adam_partials_offset(int ntensors) { return (5 * (int64_t)ntensors + 1) & ~(int64_t)1; }
+inline int64_t adam_ws_floats(int ntensors, int nblocks) { return adam_partials_offset(ntensors) + 2 * (int64_t)nblocks; }
+// ws_clip: null (c = grad_scale), or the LARS-layout workspace whose head holds c
+void launch_lamb_moments_list(const AdamList& list, int tensor_base, int block_base, int nblocks, int grad_dtype,
+                              const AdamTensor* table, const float* ws_clip, float grad_scale, float* ws, int ntensors,
+                              hipStream_t stream);
+// trust: sum the (p^2, u^2) partials and form trust ratios (LAMB); otherwise trust 1 and no partial is read.
+// grad_partials (AdamW with clipping): ws_clip holds the square sums of a gradient pass and receives c, G, clip
+// in its head, as launch_lars_finalize writes them.
+void launch_adam_finalize(const AdamTensor* table, int ntensors, const float* lr_dev, bool trust, bool grad_partials,
+                          float grad_scale, float max_grad_norm, float* ws_clip, float* ws, hipStream_t stream);
+// ema.ema[t] / omd may be null (no weight EMA)
+void launch_lamb_apply_list(const AdamList& list, int tensor_base, int nblocks, const EmaSlots* ema, const float* omd,
+                            const AdamTensor* table, const float* ws, int ntensors, hipStream_t stream);
+void launch_adamw_list(const AdamList& list, int tensor_base, int nblocks, int grad_dtype, const EmaSlots* ema,
+                       const float* omd, const AdamTensor* table, const float* ws_clip, float grad_scale,
+                       const float* ws, int ntensors, hipStream_t stream);
 
 // ---- elementwise reductions for the collectives (reduce.hip) --------------------------------
 constexpr int kMaxReduceSrc = 8;

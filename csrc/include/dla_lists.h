@@ -38,6 +38,16 @@ struct EmaEntry {
   int64_t numel;
 };
 
+// FusedLAMB / FusedAdamW: fp32 parameter (or master), gradient, the two fp32 moments and the optional shadow.
+struct AdamEntry {
+  float* param;
+  const void* grad;      // float* or bf16*; unused (null) by the LAMB apply pass
+  float* m;              // exp_avg
+  float* v;              // exp_avg_sq
+  uint16_t* param_bf16;  // optional bf16 shadow copy of the parameter (null = skip)
+  int64_t numel;
+};
+
 // By-value tensor lists (kernel arguments, no device table): one launch covers up to kMaxList tensors; used
 // when tensor addresses change between steps. Entry t owns blocks [prefix[t], prefix[t + 1]) of the launch,
 // so prefix[ntensors] (index kMaxList in a full list, hence the + 1) is the launch's block count.
@@ -51,6 +61,7 @@ struct TensorList {
 using SgdList = TensorList<SgdEntry>;
 using PackList = TensorList<PackEntry>;
 using EmaList = TensorList<EmaEntry>;
+using AdamList = TensorList<AdamEntry>;
 
 // Weight EMA (exponential moving average), fused into the list update kernels: slot t is the fp32 average of
 // list entry t, advanced from the fp32 value the update just stored, ema = fmaf(omd, p_new - ema, ema) with
@@ -70,6 +81,10 @@ static_assert(sizeof(SgdList) == 1416 && offsetof(SgdList, e) == 136, "SgdList l
 static_assert(sizeof(PackList) == 904 && offsetof(PackList, e) == 136, "PackList layout");
 static_assert(sizeof(EmaList) == 1160 && offsetof(EmaList, e) == 136, "EmaList layout");
 static_assert(sizeof(LarsList) == 1424 && offsetof(LarsList, tensor_base) == 1416, "LarsList layout");
+static_assert(sizeof(AdamEntry) == 48 && offsetof(AdamEntry, v) == 24 && offsetof(AdamEntry, numel) == 40,
+              "AdamEntry layout");
+static_assert(sizeof(AdamList) == 1672 && offsetof(AdamList, e) == 136, "AdamList layout");
+static_assert(sizeof(AdamList) + sizeof(EmaSlots) == 1928, "AdamList + EmaSlots kernel arguments");
 
 // Cuts a sequence of entries into by-value launches. It launches nothing: a caller adds (and so checks) every
 // tensor first and runs the launches of finish() afterwards, so a bad tensor anywhere raises with nothing done.

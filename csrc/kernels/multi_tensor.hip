@@ -353,8 +353,33 @@ void launch_unpack(const PackEntry* entries, const int32_t* prefix, int ntensors
 // Fused LARS (You et al. 2017) and tensor-list L2 norms; layout and formula in dla_kernels.h.
 // HBM-bound like SGD: the square-sum pass adds one read of p and g to the update's traffic.
 // --------------------------------------------------------------------------------------------
-// Square sums of one chunk: 16 elements per thread accumulated in fp32 in a fixed order, then the
-// wave butterfly, then the 4 waves through LDS. One plain 8-byte store per block.
+// The block's two sums from every thread's two: the wave butterfly, then the 4 waves through LDS in wave
+// order. One plain 8-byte store per block (no atomics: bitwise reproducible).
+__device__ __forceinline__ void block_sum2_store(float a, float b, float* out) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  __shared__ float sm[2][kMTBlock / kWave];
+  const int wave = threadIdx.x / kWave;
+  if (threadIdx.x % kWave == 0) {
+    sm[0][wave] = a;
+    sm[1][wave] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = sm[0][0];
+    b = sm[1][0];
+#pragma unroll
+    for (int w = 1; w < kMTBlock / kWave; ++w) {
+      a += sm[0][w];
+      b += sm[1][w];
+    }
+    out[0] = a;
+    out[1] = b;
+  }
+}
+
+// Square sums of one chunk: 16 elements per thread accumulated in fp32 in a fixed order, then
+// block_sum2_store.
 template <typename G>
 __global__ __launch_bounds__(kMTBlock) void sqsum_list_kernel(LarsList list, float* __restrict__ partials) {
   const auto c = find_chunk(list.l.prefix, list.l.ntensors, list.l.e);
@@ -377,26 +402,7 @@ __global__ __launch_bounds__(kMTBlock) void sqsum_list_kernel(LarsList list, flo
         sg = fmaf(gv, gv, sg);
         if (p) sp = fmaf(p[i], p[i], sp);
       });
-  sp = wave_sum(sp);
-  sg = wave_sum(sg);
-  __shared__ float sm[2][kMTBlock / kWave];
-  const int wave = threadIdx.x / kWave;
-  if (threadIdx.x % kWave == 0) {
-    sm[0][wave] = sp;
-    sm[1][wave] = sg;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = sm[0][0], b = sm[1][0];
-#pragma unroll
-    for (int w = 1; w < kMTBlock / kWave; ++w) {
-      a += sm[0][w];
-      b += sm[1][w];
-    }
-    float* out = partials + 2 * ((int64_t)list.block_base + blockIdx.x);
-    out[0] = a;
-    out[1] = b;
-  }
+  block_sum2_store(sp, sg, partials + 2 * ((int64_t)list.block_base + blockIdx.x));
 }
 
 // One block of 16 waves. Wave w sums the partial ranges of tensors w, w + 16, ... (lane-strided, then
@@ -530,6 +536,302 @@ void launch_lars_ema_list(const LarsList& list, const EmaSlots& ema, const float
   dispatch_dtype(grad_dtype, [&](auto g) {
     hipLaunchKernelGGL((lars_ema_list_kernel<tag_t<decltype(g)>>), dim3(nblocks), dim3(kMTBlock), 0, stream, list, ema,
                        omd, table, ws);
+  });
+}
+
+// --------------------------------------------------------------------------------------------
+// Fused LAMB (You et al. 2019) and AdamW; passes, formula and layouts in dla_kernels.h. HBM-bound:
+// with bf16 gradients and shadows the LAMB moments pass moves 22 B/elem, its apply pass 18, the
+// one-pass AdamW update 28 (+ 8 each for the weight EMA). Times: profiles/lamb/README.md.
+// --------------------------------------------------------------------------------------------
+struct AdamCoef {
+  float c;                   // grad_scale * clip
+  float b1, omb1, b2, omb2;  // beta, 1 - beta
+  float bc1, bc2;            // 1 - beta^k
+  float eps, wd, alpha;      // alpha = lr * trust
+};
+
+// 1 - beta^k from ln(beta): relative error ~1e-7 for every k, where a running fp32 product beta^k drifts.
+__device__ __forceinline__ float bias_correction(int k, float ln_beta) {
+  return -expm1f(__fmul_rn((float)k, ln_beta));
+}
+
+__device__ __forceinline__ AdamCoef adam_coef(const AdamTensor& r, float c, float bc1, float bc2, float alpha) {
+  return {c, r.beta1, r.omb1, r.beta2, r.omb2, bc1, bc2, r.eps, r.weight_decay, alpha};
+}
+
+// One element. kGrad: the gradient enters the moments; kApply: the parameter is stepped, otherwise p^2 and
+// u^2 are accumulated. Both LAMB passes and the AdamW pass form u by this one expression (plain divisions
+// and square root: the bound of the tests leaves no room for the approximate forms).
+template <bool kGrad, bool kApply>
+__device__ __forceinline__ void adam_elem(const AdamCoef& h, float& p, float g, float& m, float& v, float& sp,
+                                          float& su) {
+  if constexpr (kGrad) {
+    const float gh = h.c * g;
+    m = fmaf(h.b1, m, h.omb1 * gh);
+    v = fmaf(h.b2, v, (h.omb2 * gh) * gh);
+  }
+  const float u = fmaf(h.wd, p, (m / h.bc1) / (sqrtf(v / h.bc2) + h.eps));
+  if constexpr (kApply) {
+    p = fmaf(-h.alpha, u, p);
+  } else {
+    sp = fmaf(p, p, sp);
+    su = fmaf(u, u, su);
+  }
+}
+
+// update_chunk's sibling for two moment buffers. Reads p, m, v and with kGrad g (fp32 or bf16); writes m, v
+// with kGrad, and p, the optional bf16 shadow and with kEma the average with kApply.
+template <typename G, bool kGrad, bool kApply, bool kEma>
+__device__ __forceinline__ void adam_chunk(const Chunk<AdamEntry>& c, const AdamCoef& h, float* ema, float omd,
+                                           float& sp, float& su) {
+  static_assert(kApply || !kEma, "the average follows the stored parameter");
+  float* __restrict__ p = c.e.param;
+  const G* __restrict__ g = reinterpret_cast<const G*>(c.e.grad);
+  float* __restrict__ m = c.e.m;
+  float* __restrict__ v = c.e.v;
+  bf16_t* __restrict__ pb = kApply ? c.e.param_bf16 : nullptr;
+  float* __restrict__ ev = ema;
+  for_chunk(
+      c, aligned16(p, kGrad ? g : nullptr, m, v, kEma ? ev : nullptr, pb),
+      [&](int64_t i) {
+        const float4_t pv = *reinterpret_cast<const float4_t*>(p + i);
+        float4_t gv{0, 0, 0, 0};
+        if constexpr (kGrad) gv = load4_f32(g + i);
+        const float4_t mv = *reinterpret_cast<const float4_t*>(m + i);
+        const float4_t vv = *reinterpret_cast<const float4_t*>(v + i);
+        float4_t ea{0, 0, 0, 0};
+        if constexpr (kEma) ea = *reinterpret_cast<const float4_t*>(ev + i);
+        float po[4] = {pv.x, pv.y, pv.z, pv.w}, mo[4] = {mv.x, mv.y, mv.z, mv.w}, vo[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) adam_elem<kGrad, kApply>(h, po[j], gv[j], mo[j], vo[j], sp, su);
+        if constexpr (kGrad) {
+          *reinterpret_cast<float4_t*>(m + i) = float4_t{mo[0], mo[1], mo[2], mo[3]};
+          *reinterpret_cast<float4_t*>(v + i) = float4_t{vo[0], vo[1], vo[2], vo[3]};
+        }
+        if constexpr (kApply) {
+          *reinterpret_cast<float4_t*>(p + i) = float4_t{po[0], po[1], po[2], po[3]};
+          if constexpr (kEma) {
+            *reinterpret_cast<float4_t*>(ev + i) =
+                float4_t{fmaf(omd, po[0] - ea.x, ea.x), fmaf(omd, po[1] - ea.y, ea.y), fmaf(omd, po[2] - ea.z, ea.z),
+                         fmaf(omd, po[3] - ea.w, ea.w)};
+          }
+          if (pb) {
+            *reinterpret_cast<ushort4_t*>(pb + i) =
+                ushort4_t{f32_to_bf16(po[0]), f32_to_bf16(po[1]), f32_to_bf16(po[2]), f32_to_bf16(po[3])};
+          }
+        }
+      },
+      [&](int64_t i) {
+        float po = p[i], mo = m[i], vo = v[i], gv = 0.f;
+        if constexpr (kGrad) gv = Cvt<G>::to_f32(g[i]);
+        adam_elem<kGrad, kApply>(h, po, gv, mo, vo, sp, su);
+        if constexpr (kGrad) {
+          m[i] = mo;
+          v[i] = vo;
+        }
+        if constexpr (kApply) {
+          p[i] = po;
+          if constexpr (kEma) {
+            const float ea = ev[i];
+            ev[i] = fmaf(omd, po - ea, ea);
+          }
+          if (pb) pb[i] = f32_to_bf16(po);
+        }
+      });
+}
+
+// LAMB pass 1: the moments, and this block's (sum p^2, sum u^2) with u formed in registers and never stored.
+// The finalize has not committed this step's count yet, so k = step + 1.
+template <typename G>
+__global__ __launch_bounds__(kMTBlock) void lamb_moments_list_kernel(AdamList list, int tensor_base, int block_base,
+                                                                     const AdamTensor* __restrict__ table,
+                                                                     const float* __restrict__ ws_clip,
+                                                                     float grad_scale, float* __restrict__ partials) {
+  const auto ch = find_chunk(list.prefix, list.ntensors, list.e);
+  const AdamTensor r = table[tensor_base + ch.t];
+  const int k = r.step[0] + 1;
+  const AdamCoef h = adam_coef(r, ws_clip ? ws_clip[0] : grad_scale, bias_correction(k, r.ln_beta1),
+                               bias_correction(k, r.ln_beta2), 0.f);
+  float sp = 0.f, su = 0.f;
+  adam_chunk<G, true, false, false>(ch, h, nullptr, 0.f, sp, su);
+  block_sum2_store(sp, su, partials + 2 * ((int64_t)block_base + blockIdx.x));
+}
+
+// One block, the shape of lars_finalize_kernel (16 waves, the next table row fetched ahead). trust: wave w
+// sums the (p^2, u^2) partials of tensors w, w + 16, ...; grad_partials: the same walk over the (., g^2)
+// partials of a gradient square-sum pass in ws_clip, whose total gives G, clip and c as in LARS. Then every
+// thread forms its tensors' bias corrections, trust and alpha, and commits step + 1.
+__global__ __launch_bounds__(kFinBlock) void adam_finalize_kernel(const AdamTensor* __restrict__ table, int ntensors,
+                                                                  const float* __restrict__ lr_dev, int trust,
+                                                                  int grad_partials, float grad_scale,
+                                                                  float max_grad_norm, float* ws_clip, float* ws) {
+  float* alpha = ws;
+  float* bc = ws + ntensors;
+  float* norms = ws + 3 * (int64_t)ntensors;
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  if (trust || grad_partials) {  // uniform over the block
+    const float2* partials = reinterpret_cast<const float2*>(
+        trust ? ws + adam_partials_offset(ntensors) : ws_clip + lars_partials_offset(ntensors));
+    float total = 0.f;
+    int nb = 0, ne = 0;
+    if (wave < ntensors) {
+      nb = table[wave].part_begin;
+      ne = table[wave].part_end;
+    }
+    for (int t = wave; t < ntensors; t += kFinWaves) {
+      const int b = nb, e = ne;
+      if (t + kFinWaves < ntensors) {
+        nb = table[t + kFinWaves].part_begin;
+        ne = table[t + kFinWaves].part_end;
+      }
+      float sa = 0.f, sb = 0.f;
+      for (int i = b + lane; i < e; i += kWave) {
+        const float2 v = partials[i];
+        sa += v.x;
+        sb += v.y;
+      }
+      sa = wave_sum(sa);
+      sb = wave_sum(sb);
+      total += sb;
+      if (trust && lane == 0) {
+        norms[2 * t] = sa;
+        norms[2 * t + 1] = sb;
+      }
+    }
+    __shared__ float sm[kFinWaves];
+    if (lane == 0) sm[wave] = total;
+    __syncthreads();  // also orders the squared sums stored above before the loads below
+    if (grad_partials && threadIdx.x == 0) {
+      total = sm[0];
+#pragma unroll
+      for (int w = 1; w < kFinWaves; ++w) total += sm[w];
+      const float gnorm = grad_scale * sqrtf(total);
+      const float clip = max_grad_norm > 0.f ? fminf(1.f, max_grad_norm / (gnorm + 1e-6f)) : 1.f;
+      ws_clip[0] = grad_scale * clip;
+      ws_clip[1] = gnorm;
+      ws_clip[2] = clip;
+      ws_clip[3] = 0.f;
+    }
+  }
+  for (int t = threadIdx.x; t < ntensors; t += kFinBlock) {
+    const AdamTensor r = table[t];
+    const int k = r.step[0] + 1;
+    float tr = 1.f;
+    if (trust) {
+      const float wn = sqrtf(norms[2 * t]), un = sqrtf(norms[2 * t + 1]);
+      if (r.adapt && wn > 0.f && un > 0.f) tr = wn / un;
+      norms[2 * t] = wn;
+      norms[2 * t + 1] = un;
+    }
+    alpha[t] = lr_dev[r.group] * tr;
+    bc[2 * t] = bias_correction(k, r.ln_beta1);
+    bc[2 * t + 1] = bias_correction(k, r.ln_beta2);
+    r.step[0] = k;
+  }
+}
+
+// What the passes after the finalize read of it: table row, alpha and the bias corrections of row `row`.
+__device__ __forceinline__ AdamCoef adam_coef_final(const AdamTensor* __restrict__ table, const float* __restrict__ ws,
+                                                    int ntensors, int row, float c) {
+  return adam_coef(table[row], c, ws[ntensors + 2 * row], ws[ntensors + 2 * row + 1], ws[row]);
+}
+
+// LAMB pass 3: u again from p, m, v (no gradient read, no u buffer), p -= alpha u.
+template <bool kEma>
+__device__ __forceinline__ void lamb_apply_body(const Chunk<AdamEntry>& ch, int row, const AdamTensor* table,
+                                                const float* ws, int ntensors, float* ema, float omd) {
+  float sp = 0.f, su = 0.f;  // unused: kApply
+  adam_chunk<float, false, true, kEma>(ch, adam_coef_final(table, ws, ntensors, row, 0.f), ema, omd, sp, su);
+}
+
+__global__ __launch_bounds__(kMTBlock) void lamb_apply_list_kernel(AdamList list, int tensor_base,
+                                                                   const AdamTensor* __restrict__ table,
+                                                                   const float* __restrict__ ws, int ntensors) {
+  const auto ch = find_chunk(list.prefix, list.ntensors, list.e);
+  lamb_apply_body<false>(ch, tensor_base + ch.t, table, ws, ntensors, nullptr, 0.f);
+}
+
+__global__ __launch_bounds__(kMTBlock) void lamb_apply_ema_list_kernel(AdamList list, int tensor_base, EmaSlots ema,
+                                                                       const float* __restrict__ omd,
+                                                                       const AdamTensor* __restrict__ table,
+                                                                       const float* __restrict__ ws, int ntensors) {
+  const auto ch = find_chunk(list.prefix, list.ntensors, list.e);
+  lamb_apply_body<true>(ch, tensor_base + ch.t, table, ws, ntensors, ema.ema[ch.t], omd[0]);
+}
+
+// AdamW: moments and update in one pass, after the finalize (alpha = lr, no norm work).
+template <typename G, bool kEma>
+__device__ __forceinline__ void adamw_body(const Chunk<AdamEntry>& ch, int row, const AdamTensor* table,
+                                           const float* ws_clip, float grad_scale, const float* ws, int ntensors,
+                                           float* ema, float omd) {
+  float sp = 0.f, su = 0.f;  // unused: kApply
+  adam_chunk<G, true, true, kEma>(
+      ch, adam_coef_final(table, ws, ntensors, row, ws_clip ? ws_clip[0] : grad_scale), ema, omd, sp, su);
+}
+
+template <typename G>
+__global__ __launch_bounds__(kMTBlock) void adamw_list_kernel(AdamList list, int tensor_base,
+                                                              const AdamTensor* __restrict__ table,
+                                                              const float* __restrict__ ws_clip, float grad_scale,
+                                                              const float* __restrict__ ws, int ntensors) {
+  const auto ch = find_chunk(list.prefix, list.ntensors, list.e);
+  adamw_body<G, false>(ch, tensor_base + ch.t, table, ws_clip, grad_scale, ws, ntensors, nullptr, 0.f);
+}
+
+template <typename G>
+__global__ __launch_bounds__(kMTBlock) void adamw_ema_list_kernel(AdamList list, int tensor_base, EmaSlots ema,
+                                                                  const float* __restrict__ omd,
+                                                                  const AdamTensor* __restrict__ table,
+                                                                  const float* __restrict__ ws_clip, float grad_scale,
+                                                                  const float* __restrict__ ws, int ntensors) {
+  const auto ch = find_chunk(list.prefix, list.ntensors, list.e);
+  adamw_body<G, true>(ch, tensor_base + ch.t, table, ws_clip, grad_scale, ws, ntensors, ema.ema[ch.t], omd[0]);
+}
+
+void launch_lamb_moments_list(const AdamList& list, int tensor_base, int block_base, int nblocks, int grad_dtype,
+                              const AdamTensor* table, const float* ws_clip, float grad_scale, float* ws, int ntensors,
+                              hipStream_t stream) {
+  if (nblocks <= 0 || list.ntensors <= 0) return;
+  float* partials = ws + adam_partials_offset(ntensors);
+  dispatch_dtype(grad_dtype, [&](auto g) {
+    hipLaunchKernelGGL((lamb_moments_list_kernel<tag_t<decltype(g)>>), dim3(nblocks), dim3(kMTBlock), 0, stream, list,
+                       tensor_base, block_base, table, ws_clip, grad_scale, partials);
+  });
+}
+
+void launch_adam_finalize(const AdamTensor* table, int ntensors, const float* lr_dev, bool trust, bool grad_partials,
+                          float grad_scale, float max_grad_norm, float* ws_clip, float* ws, hipStream_t stream) {
+  if (ntensors <= 0) return;
+  hipLaunchKernelGGL(adam_finalize_kernel, dim3(1), dim3(kFinBlock), 0, stream, table, ntensors, lr_dev, trust ? 1 : 0,
+                     grad_partials ? 1 : 0, grad_scale, max_grad_norm, ws_clip, ws);
+}
+
+void launch_lamb_apply_list(const AdamList& list, int tensor_base, int nblocks, const EmaSlots* ema, const float* omd,
+                            const AdamTensor* table, const float* ws, int ntensors, hipStream_t stream) {
+  if (nblocks <= 0 || list.ntensors <= 0) return;
+  if (ema) {
+    hipLaunchKernelGGL(lamb_apply_ema_list_kernel, dim3(nblocks), dim3(kMTBlock), 0, stream, list, tensor_base, *ema,
+                       omd, table, ws, ntensors);
+  } else {
+    hipLaunchKernelGGL(lamb_apply_list_kernel, dim3(nblocks), dim3(kMTBlock), 0, stream, list, tensor_base, table, ws,
+                       ntensors);
+  }
+}
+
+void launch_adamw_list(const AdamList& list, int tensor_base, int nblocks, int grad_dtype, const EmaSlots* ema,
+                       const float* omd, const AdamTensor* table, const float* ws_clip, float grad_scale,
+                       const float* ws, int ntensors, hipStream_t stream) {
+  if (nblocks <= 0 || list.ntensors <= 0) return;
+  dispatch_dtype(grad_dtype, [&](auto g) {
+    using G = tag_t<decltype(g)>;
+    if (ema) {
+      hipLaunchKernelGGL((adamw_ema_list_kernel<G>), dim3(nblocks), dim3(kMTBlock), 0, stream, list, tensor_base, *ema,
+                         omd, table, ws_clip, grad_scale, ws, ntensors);
+    } else {
+      hipLaunchKernelGGL((adamw_list_kernel<G>), dim3(nblocks), dim3(kMTBlock), 0, stream, list, tensor_base, table,
+                         ws_clip, grad_scale, ws, ntensors);
+    }
   });
 }
 

@@ -4,6 +4,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cmath>
 #include <vector>
 
 #include "dla_kernels.h"
@@ -389,6 +390,204 @@ void lars_ema_step_list(LarsPlan& plan, std::vector<at::Tensor> params, std::vec
   plan.run(params, grads, moms, shadows, true, grad_scale, max_grad_norm, &emas, &omd);
 }
 
+// ------------------------------------------------------------------------------------------
+// Fused LAMB / AdamW (formula and passes: dla_kernels.h). AdamPlan owns what is static for one set of
+// participating tensors: the device table (partial ranges, group, hyper-parameters, the address of each
+// tensor's int32 update count), the workspace, and for clipping a LARS-layout workspace and table for the
+// gradient square sums. Nothing is read back to the host; the finalize launch advances the counts.
+// ------------------------------------------------------------------------------------------
+class AdamPlan {
+ public:
+  AdamPlan(bool trust, std::vector<int64_t> numels, std::vector<int64_t> groups, std::vector<bool> adapt,
+           std::vector<double> weight_decay, std::vector<double> beta1, std::vector<double> beta2,
+           std::vector<double> eps, std::vector<at::Tensor> steps, at::Tensor lr_dev, at::Tensor like)
+      : trust_(trust), numels_(std::move(numels)), steps_(std::move(steps)) {
+    const size_t T = numels_.size();
+    TORCH_CHECK(T > 0 && T < (size_t)1 << 24, "AdamPlan: bad tensor count ", T);
+    TORCH_CHECK(groups.size() == T && adapt.size() == T && weight_decay.size() == T && beta1.size() == T &&
+                    beta2.size() == T && eps.size() == T && steps_.size() == T,
+                "AdamPlan: per-tensor lists must have one entry per tensor");
+    TORCH_CHECK(like.is_cuda(), "AdamPlan: GPU tensors only");
+    check_dev(lr_dev, "lr_dev");
+    TORCH_CHECK(lr_dev.scalar_type() == at::kFloat && lr_dev.device() == like.device() && lr_dev.is_contiguous(),
+                "AdamPlan: lr_dev must be a contiguous fp32 tensor on the parameters' device");
+    lr_dev_ = lr_dev;
+    const int chunk = mt_chunk_elems();
+    std::vector<AdamTensor> rows(T);
+    std::vector<LarsTensor> clip_rows(T);
+    int64_t blocks = 0;
+    for (size_t i = 0; i < T; ++i) {
+      TORCH_CHECK(numels_[i] >= 0, "AdamPlan: negative numel");
+      TORCH_CHECK(groups[i] >= 0 && groups[i] < lr_dev_.numel(), "AdamPlan: group ", groups[i], " out of range");
+      TORCH_CHECK(eps[i] > 0 && beta1[i] >= 0 && beta1[i] < 1 && beta2[i] >= 0 && beta2[i] < 1,
+                  "AdamPlan: eps > 0 and betas in [0, 1) required");
+      check_step(steps_[i], like, i);
+      AdamTensor& r = rows[i];
+      r.part_begin = (int32_t)blocks;
+      blocks += (numels_[i] + chunk - 1) / chunk;
+      TORCH_CHECK(blocks < ((int64_t)1 << 30), "AdamPlan: too many chunks");
+      r.part_end = (int32_t)blocks;
+      r.group = (int32_t)groups[i];
+      r.adapt = trust && adapt[i] ? 1 : 0;
+      r.weight_decay = (float)weight_decay[i];
+      r.eps = (float)eps[i];
+      r.beta1 = (float)beta1[i];
+      r.beta2 = (float)beta2[i];
+      r.omb1 = (float)(1.0 - beta1[i]);
+      r.omb2 = (float)(1.0 - beta2[i]);
+      r.ln_beta1 = (float)std::log(beta1[i]);
+      r.ln_beta2 = (float)std::log(beta2[i]);
+      r.step = steps_[i].data_ptr<int32_t>();
+      clip_rows[i] = LarsTensor{r.part_begin, r.part_end, 0, 0, 0.f, 0.f, 0.f, 0.f};
+    }
+    nblocks_ = (int)blocks;
+    table_ = upload(rows.data(), rows.size() * sizeof(AdamTensor), like.device());
+    clip_table_ = upload(clip_rows.data(), clip_rows.size() * sizeof(LarsTensor), like.device());
+    ws_ = at::zeros({adam_ws_floats((int)T, nblocks_)}, like.options().dtype(at::kFloat));
+    ws_clip_ = at::zeros({lars_ws_floats((int)T, nblocks_)}, like.options().dtype(at::kFloat));
+  }
+
+  bool trust() const { return trust_; }
+  int ntensors() const { return (int)numels_.size(); }
+  at::Tensor grad_norm() const { return ws_clip_.narrow(0, 1, 1); }  // G of the last step with clipping on
+  at::Tensor alpha() const { return ws_.narrow(0, 0, ntensors()); }  // lr * trust
+  // [T, 2]: (1 - beta1^k, 1 - beta2^k) of the last step
+  at::Tensor bias_corrections() const { return ws_.narrow(0, ntensors(), 2 * (int64_t)ntensors()).view({-1, 2}); }
+  // [T, 2]: (||p_t||, ||u_t||) of the last step (LAMB)
+  at::Tensor norms() const { return ws_.narrow(0, 3 * (int64_t)ntensors(), 2 * (int64_t)ntensors()).view({-1, 2}); }
+  int last_launches() const { return launches_; }
+
+  void run(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+           const std::vector<at::Tensor>& ms, const std::vector<at::Tensor>& vs,
+           const std::vector<c10::optional<at::Tensor>>& shadows, const std::vector<at::Tensor>& steps,
+           double grad_scale, double max_grad_norm, const std::vector<at::Tensor>* emas = nullptr,
+           const at::Tensor* omd = nullptr) {
+    const char* op = trust_ ? "lamb" : "adamw";
+    const size_t T = numels_.size();
+    TORCH_CHECK(grads.size() == T, op, ": the plan was built for ", T, " tensors, got ", grads.size());
+    TORCH_CHECK(params.size() == T && ms.size() == T && vs.size() == T && steps.size() == T, op,
+                ": a parameter, two moments and a step count per gradient are needed");
+    TORCH_CHECK(shadows.empty() || shadows.size() == T, op, ": shadow list size mismatch");
+    TORCH_CHECK(!emas || emas->size() == T, op, ": ema list size mismatch");
+    TORCH_CHECK(max_grad_norm >= 0, op, ": max_grad_norm must be >= 0");
+    if (emas) check_omd(*omd, ws_, op);
+    // every launch is built, and so every tensor checked, before the first one runs; empty tensors keep their
+    // slot, so that slot t of a launch is table row tensor_base + t
+    ListBatcher<AdamEntry> lists(op, /*keep_empty=*/true);
+    for (size_t i = 0; i < T; ++i) {
+      const at::Tensor& g = grads[i];
+      const at::Tensor& p = params[i];
+      check_dev(g, "grad");
+      check_dev(p, "param");
+      TORCH_CHECK(g.device() == ws_.device(), op, ": tensor ", i, " is on another device than the plan");
+      TORCH_CHECK(g.numel() == numels_[i], op, ": tensor ", i, " has ", g.numel(), " elements, the plan ", numels_[i]);
+      TORCH_CHECK(p.scalar_type() == at::kFloat && p.device() == g.device(), op,
+                  ": parameters/masters must be fp32 on the gradients' device");
+      TORCH_CHECK(same_layout(g, p), op, ": grad ", i, " must match its parameter's layout");
+      lists.tag(dtype_code(g));
+      AdamEntry e{};
+      e.param = p.data_ptr<float>();
+      e.grad = g.data_ptr();
+      e.numel = g.numel();
+      for (int j = 0; j < 2; ++j) {
+        const at::Tensor& m = j == 0 ? ms[i] : vs[i];
+        check_dev(m, "moment");
+        TORCH_CHECK(m.scalar_type() == at::kFloat && m.device() == g.device() && same_layout(m, p), op, ": moment ", i,
+                    " must be fp32 on the gradients' device with the parameter's layout");
+        (j == 0 ? e.m : e.v) = m.data_ptr<float>();
+      }
+      if (!shadows.empty() && shadows[i].has_value() && (*shadows[i]).defined()) {
+        const at::Tensor& s = *shadows[i];
+        check_dev(s, "bf16 shadow");
+        TORCH_CHECK(s.scalar_type() == at::kBFloat16 && s.device() == g.device() && same_layout(s, p), op,
+                    ": bad shadow");
+        e.param_bf16 = reinterpret_cast<uint16_t*>(s.data_ptr());
+      }
+      check_step(steps[i], ws_, i);
+      TORCH_CHECK(steps[i].data_ptr() == steps_[i].data_ptr(), op, ": step count ", i,
+                  " is not the tensor the plan was built with");
+      float* ema = nullptr;
+      if (emas) {
+        check_ema((*emas)[i], p, i, op);
+        ema = (*emas)[i].data_ptr<float>();
+      }
+      lists.add(e, ema);
+    }
+    const auto& launches = lists.finish();
+    TORCH_CHECK(lists.total_blocks() == nblocks_, op, ": chunk count changed since the plan was built");
+    hipStream_t st = current_stream(ws_);
+    const bool clip = max_grad_norm > 0;
+    const float gs = (float)grad_scale, mgn = (float)max_grad_norm;
+    const AdamTensor* table = reinterpret_cast<const AdamTensor*>(table_.data_ptr());
+    float* ws = ws_.data_ptr<float>();
+    float* wsc = clip ? ws_clip_.data_ptr<float>() : nullptr;
+    const float* lr = lr_dev_.data_ptr<float>();
+    const float* omdp = emas ? omd->data_ptr<float>() : nullptr;
+    if (clip)  // gradient square sums only: the SgdList of the square-sum kernel with a null parameter
+      for (const auto& L : launches) {
+        LarsList gl{};
+        gl.l.ntensors = L.list.ntensors;
+        for (int t = 0; t <= L.list.ntensors; ++t) gl.l.prefix[t] = L.list.prefix[t];
+        for (int t = 0; t < L.list.ntensors; ++t) {
+          gl.l.e[t].grad = L.list.e[t].grad;
+          gl.l.e[t].numel = L.list.e[t].numel;
+        }
+        gl.tensor_base = L.tensor_base;
+        gl.block_base = L.block_base;
+        launch_sqsum_list(gl, L.blocks, L.tag, wsc, (int)T, st);
+      }
+    if (trust_) {
+      if (clip)
+        launch_lars_finalize(reinterpret_cast<const LarsTensor*>(clip_table_.data_ptr()), (int)T, nullptr, gs, mgn, wsc,
+                             st);
+      for (const auto& L : launches)
+        launch_lamb_moments_list(L.list, L.tensor_base, L.block_base, L.blocks, L.tag, table, wsc, gs, ws, (int)T, st);
+      launch_adam_finalize(table, (int)T, lr, true, false, gs, mgn, wsc, ws, st);
+      for (const auto& L : launches)
+        launch_lamb_apply_list(L.list, L.tensor_base, L.blocks, emas ? &L.ema : nullptr, omdp, table, ws, (int)T, st);
+      launches_ = (int)launches.size() * (clip ? 3 : 2) + (clip ? 2 : 1);
+    } else {
+      launch_adam_finalize(table, (int)T, lr, false, clip, gs, mgn, wsc, ws, st);
+      for (const auto& L : launches)
+        launch_adamw_list(L.list, L.tensor_base, L.blocks, L.tag, emas ? &L.ema : nullptr, omdp, table, wsc, gs, ws,
+                          (int)T, st);
+      launches_ = (int)launches.size() * (clip ? 2 : 1) + 1;
+    }
+  }
+
+ private:
+  static void check_step(const at::Tensor& s, const at::Tensor& like, size_t i) {
+    TORCH_CHECK(s.is_cuda() && s.device() == like.device() && s.scalar_type() == at::kInt && s.numel() == 1,
+                "lamb/adamw: step count ", i, " must be a one-element int32 tensor on the parameters' device");
+  }
+
+  bool trust_;
+  std::vector<int64_t> numels_;
+  std::vector<at::Tensor> steps_;
+  at::Tensor table_, clip_table_, ws_, ws_clip_, lr_dev_;
+  int nblocks_ = 0, launches_ = 0;
+};
+
+// lamb_step_list / adamw_step_list (kTrust: the kind of plan each takes), and their _ema forms, which also advance
+// emas[i] from the fp32 value the update stores, in the update launches.
+template <bool kTrust>
+void adam_step_list(AdamPlan& plan, std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                    std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
+                    std::vector<c10::optional<at::Tensor>> shadows, std::vector<at::Tensor> steps, double grad_scale,
+                    double max_grad_norm) {
+  TORCH_CHECK(plan.trust() == kTrust, "lamb/adamw: the plan was built for the other optimizer");
+  plan.run(params, grads, ms, vs, shadows, steps, grad_scale, max_grad_norm);
+}
+
+template <bool kTrust>
+void adam_ema_step_list(AdamPlan& plan, std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
+                        std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
+                        std::vector<c10::optional<at::Tensor>> shadows, std::vector<at::Tensor> steps,
+                        std::vector<at::Tensor> emas, at::Tensor omd, double grad_scale, double max_grad_norm) {
+  TORCH_CHECK(plan.trust() == kTrust, "lamb/adamw: the plan was built for the other optimizer");
+  plan.run(params, grads, ms, vs, shadows, steps, grad_scale, max_grad_norm, &emas, &omd);
+}
+
 // (per_tensor[T], total[1]) = scale * (||t||_2 of each tensor, of all of them together), fp32.
 // A one-off plan per call: a host-built table uploaded synchronously and a fresh workspace that the
 // results are views of -- not for the inside of a step or a graph capture (FusedLARS caches its plan).
@@ -719,6 +918,22 @@ void bind_ops(pybind11::module& m) {
       .def("last_launches", &LarsPlan::last_launches);
   m.def("lars_step_list", &lars_step_list,
         "fused LARS over by-value tensor lists: square sums, finalize (norms, clip, trust), update");
+  pybind11::class_<AdamPlan>(m, "AdamPlan")
+      .def(pybind11::init<bool, std::vector<int64_t>, std::vector<int64_t>, std::vector<bool>, std::vector<double>,
+                          std::vector<double>, std::vector<double>, std::vector<double>, std::vector<at::Tensor>,
+                          at::Tensor, at::Tensor>())
+      .def("grad_norm", &AdamPlan::grad_norm)
+      .def("alpha", &AdamPlan::alpha)
+      .def("bias_corrections", &AdamPlan::bias_corrections)
+      .def("norms", &AdamPlan::norms)
+      .def("last_launches", &AdamPlan::last_launches);
+  m.def("lamb_step_list", &adam_step_list<true>,
+        "fused LAMB over by-value tensor lists: moments + square sums, finalize (trust, bias corrections, step "
+        "counts), apply; with max_grad_norm > 0 a gradient square-sum pass and its finalize first");
+  m.def("adamw_step_list", &adam_step_list<false>,
+        "fused AdamW over by-value tensor lists: finalize (bias corrections, step counts), one update pass");
+  m.def("lamb_ema_step_list", &adam_ema_step_list<true>, "lamb_step_list with the weight EMA in the apply launches");
+  m.def("adamw_ema_step_list", &adam_ema_step_list<false>, "adamw_step_list with the weight EMA in the update launches");
   m.def("sgd_ema_step_list", &sgd_ema_step_list,
         "sgd_step_list with the weight EMA in the same launches: ema = fmaf(omd, p_new - ema, ema), omd on the device");
   m.def("lars_ema_step_list", &lars_ema_step_list, "lars_step_list with the weight EMA in the update launches");

@@ -52,12 +52,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--momentum", type=float, default=0.5)
     p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "lamb", "adamw"],
                    help="sgd: fused momentum SGD (the reference's); lars: fused layer-wise adaptive rate scaling "
-                        "for large global batches")
+                        "for large global batches; lamb: fused LAMB (Adam moments, decoupled weight decay, "
+                        "layer-wise trust ratio); adamw: fused AdamW")
+    p.add_argument("--beta1", type=float, default=0.9, help="lamb / adamw: decay of the first moment, in [0, 1)")
+    p.add_argument("--beta2", type=float, default=0.999, help="lamb / adamw: decay of the second moment, in [0, 1)")
+    p.add_argument("--opt_eps", type=float, default=1e-6, help="lamb / adamw: epsilon added to sqrt(v), > 0")
     p.add_argument("--lars_eta", type=float, default=1e-3, help="LARS trust coefficient")
     p.add_argument("--max_grad_norm", type=float, default=0.0,
-                   help="clip gradients by their global L2 norm (0 = off; --optimizer lars only)")
+                   help="clip gradients by their global L2 norm (0 = off; --optimizer lars, lamb or adamw)")
     p.add_argument("--warmup_steps", type=int, default=0, help="linear learning-rate warmup from 0 over this many batches")
     p.add_argument("--total_steps", type=int, default=0,
                    help="polynomial learning-rate decay to 0 at this batch (0 = no decay)")
@@ -134,8 +138,12 @@ def parse_args(argv: Optional[List[str]] = None):
     config = parser.parse_args(argv)
     if config.max_grad_norm < 0:
         parser.error("--max_grad_norm must be >= 0")
-    if config.max_grad_norm > 0 and config.optimizer != "lars":
-        parser.error("--max_grad_norm needs --optimizer lars (the fused SGD does not clip)")
+    if config.max_grad_norm > 0 and config.optimizer == "sgd":
+        parser.error("--max_grad_norm needs --optimizer lars, lamb or adamw (the fused SGD does not clip)")
+    if not (0.0 <= config.beta1 < 1.0 and 0.0 <= config.beta2 < 1.0):
+        parser.error("--beta1 and --beta2 must be in [0, 1)")
+    if not config.opt_eps > 0:
+        parser.error("--opt_eps must be > 0")
     if config.warmup_steps < 0 or config.total_steps < 0:
         parser.error("--warmup_steps and --total_steps must be >= 0")
     if not 0.0 <= config.label_smoothing < 1.0:

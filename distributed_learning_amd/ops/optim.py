@@ -15,13 +15,19 @@ with the norms, trust ratios and the global-norm clip computed on the device: a 
 of launches, reads nothing back to the host, and takes its learning rate from device memory so a
 captured step follows a schedule (``set_lr``). ``poly_warmup_lr`` is the usual schedule for it.
 
-Both take ``ema_decay``: an exponential moving average of the weights advanced inside the same update
+FusedLAMB / FusedAdamW: the Adam family on the same machinery -- LAMB (You et al. 2019) is LARS's sibling
+with two moments and a trust ratio from the norm of the update, AdamW its one-pass case. Their per-tensor
+update counts live on the device and are advanced by the step itself, so a captured step moves its own bias
+corrections.
+
+All take ``ema_decay``: an exponential moving average of the weights advanced inside the same update
 launches (one more fp32 read and write per element, no launch), ``ModelEMA`` to train with it and evaluate
 from it, ``ema_decay_at`` for its warmup. Off by default.
 """
 from __future__ import annotations
 
 import contextlib
+import math
 from typing import List, Optional
 
 import torch
@@ -36,7 +42,7 @@ def ema_decay_at(t: int, decay: float, warmup: bool = False) -> float:
 
 
 class _MasterWeightsOptimizer(torch.optim.Optimizer):
-    """What FusedSGD and FusedLARS share: fp32 master copies of low-precision parameters, a
+    """What the fused optimizers share: fp32 master copies of low-precision parameters, a
     ``load_state_dict`` that keeps them (and the momentum buffers and weight averages) fp32, and the
     exponential moving average (EMA) of the weights.
 
@@ -115,13 +121,18 @@ class _MasterWeightsOptimizer(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         """torch.optim.Optimizer.load_state_dict casts floating-point state to each parameter's dtype
-        (through a policy it calls by class name); the fp32 master copies, momentum buffers and weight
-        averages of bf16 parameters must stay fp32 for a bit-exact resume, so they are re-installed afterwards."""
+        (through a policy it calls by class name); the fp32 master copies, momentum buffers, Adam moments and
+        weight averages of bf16 parameters must stay fp32 for a bit-exact resume, so they are re-installed
+        afterwards."""
         keep = {}
         for idx, st in state_dict.get("state", {}).items():
-            for k in ("master", "momentum_buffer", "ema"):
+            for k in ("master", "momentum_buffer", "ema", "exp_avg", "exp_avg_sq"):
                 if k in st and torch.is_tensor(st[k]) and st[k].dtype == torch.float32:
                     keep[(idx, k)] = st[k]
+            # FusedLAMB / FusedAdamW update counts: torch leaves a "step" entry where (and what) the checkpoint
+            # made it; the kernels need it int32 on the parameter's device, in memory of its own
+            if torch.is_tensor(st.get("step")) and st["step"].dtype == torch.int32:
+                keep[(idx, "step")] = st["step"]
         super().load_state_dict(state_dict)
         params = [p for g in self.param_groups for p in g["params"]]
         for (idx, k), v in keep.items():
@@ -272,7 +283,74 @@ def multi_tensor_l2norm(tensors, scale: float = 1.0):
     return per * scale, (torch.linalg.vector_norm(per) * scale).reshape(1)
 
 
-class FusedLARS(_MasterWeightsOptimizer):
+class _PlannedOptimizer(_MasterWeightsOptimizer):
+    """What FusedLARS and FusedLAMB / FusedAdamW share on top of that: per-group learning rates in a device array
+    the kernels read (``set_lr``), so a step captured in a HIP graph follows a schedule, and the bounded cache of
+    native plans (device table + workspace per set of participating tensors)."""
+
+    _MAX_PLANS = 4  # cached native plans (sets of participating tensors), least recently used out first
+
+    def _init_plans(self) -> None:
+        self.last_grad_norm: Optional[torch.Tensor] = None  # device tensor [1]: G of the last step
+        self._tables = {}     # participating tensors + hyper-parameters -> native plan (table, workspace)
+        self._captured = []   # plans a HIP graph was captured with, kept alive outside the cache
+        self._lr_dev = None   # fp32 [len(param_groups)] on the parameters' device
+        self._lr_seen: List[Optional[float]] = []
+        self.last_launches = 0
+
+    def set_lr(self, lr: float, group: Optional[int] = None) -> None:
+        """Set the learning rate of one param group (all when ``group`` is None): ``param_groups`` and
+        the device scalar the kernels read. A stream-ordered fill, legal between graph replays."""
+        for gi, g in enumerate(self.param_groups):
+            if group is None or gi == group:
+                g["lr"] = lr
+                if self._lr_dev is not None:
+                    self._lr_dev[gi].fill_(lr)
+                    self._lr_seen[gi] = lr
+
+    def _sync_lr(self, device) -> None:
+        """Bring the device scalars up to date with ``group["lr"]`` (schedulers write there); never while
+        a graph is being captured, where the fill would be frozen into the graph."""
+        if torch.cuda.is_current_stream_capturing():
+            if self._lr_dev is None:
+                raise RuntimeError(f"{type(self).__name__}: run a step before capturing one (the device state is "
+                                   "created there)")
+            return
+        if self._lr_dev is None or self._lr_dev.device != device or len(self._lr_seen) != len(self.param_groups):
+            self._lr_dev = torch.zeros(len(self.param_groups), dtype=torch.float32, device=device)
+            self._lr_seen = [None] * len(self.param_groups)
+            self._tables = {}  # plans hold the array
+        for gi, g in enumerate(self.param_groups):
+            if self._lr_seen[gi] != g["lr"]:
+                self._lr_dev[gi].fill_(g["lr"])
+                self._lr_seen[gi] = g["lr"]
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._lr_seen = [None] * len(self._lr_seen)
+
+    def _plan(self, key, make):
+        """The cached plan of ``key``, built by ``make()`` when missing. A plan holds a device table and a
+        workspace: only the few most recent sets are kept (a model whose set of gradient-less parameters varies
+        would otherwise grow the cache without bound)."""
+        plan = self._tables.get(key)
+        if plan is None:
+            plan = make()
+            while len(self._tables) >= self._MAX_PLANS:
+                self._tables.pop(next(iter(self._tables)))
+            self._tables[key] = plan
+        else:
+            self._tables[key] = self._tables.pop(key)  # most recently used last
+        if torch.cuda.is_current_stream_capturing() and plan not in self._captured:
+            self._captured.append(plan)  # a captured graph replays into this plan's memory: never freed
+        return plan
+
+    @staticmethod
+    def _adapt(rows):
+        return [not (g["exclude_bias_and_norm"] and p.ndim <= 1) for _, g, p in rows]
+
+
+class FusedLARS(_PlannedOptimizer):
     """Momentum SGD with layer-wise adaptive rate scaling and optional clipping by the global
     gradient norm. Per tensor ``t`` (``s`` = ``grad_scale``, sums over every tensor stepped in this call)::
 
@@ -294,8 +372,6 @@ class FusedLARS(_MasterWeightsOptimizer):
     without masters, the same formula runs in torch (also without a host read).
     """
 
-    _MAX_PLANS = 4  # cached native plans (sets of participating tensors), least recently used out first
-
     def __init__(self, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0, eta: float = 1e-3,
                  eps: float = 0.0, exclude_bias_and_norm: bool = True, grad_scale: float = 1.0,
                  max_grad_norm: float = 0.0, master_weights: bool = False, ema_decay: float = 0.0):
@@ -308,43 +384,7 @@ class FusedLARS(_MasterWeightsOptimizer):
         self.max_grad_norm = max_grad_norm
         self.master_weights = master_weights
         self._init_ema(ema_decay)
-        self.last_grad_norm: Optional[torch.Tensor] = None  # device tensor [1]: G of the last step
-        self._tables = {}     # participating tensors + hyper-parameters -> native plan (table, workspace)
-        self._captured = []   # plans a HIP graph was captured with, kept alive outside the cache
-        self._lr_dev = None   # fp32 [len(param_groups)] on the parameters' device
-        self._lr_seen: List[Optional[float]] = []
-        self.last_launches = 0
-
-    # -- learning rate -----------------------------------------------------------------------------
-    def set_lr(self, lr: float, group: Optional[int] = None) -> None:
-        """Set the learning rate of one param group (all when ``group`` is None): ``param_groups`` and
-        the device scalar the kernels read. A stream-ordered fill, legal between graph replays."""
-        for gi, g in enumerate(self.param_groups):
-            if group is None or gi == group:
-                g["lr"] = lr
-                if self._lr_dev is not None:
-                    self._lr_dev[gi].fill_(lr)
-                    self._lr_seen[gi] = lr
-
-    def _sync_lr(self, device) -> None:
-        """Bring the device scalars up to date with ``group["lr"]`` (schedulers write there); never while
-        a graph is being captured, where the fill would be frozen into the graph."""
-        if torch.cuda.is_current_stream_capturing():
-            if self._lr_dev is None:
-                raise RuntimeError("FusedLARS: run a step before capturing one (the device state is created there)")
-            return
-        if self._lr_dev is None or self._lr_dev.device != device or len(self._lr_seen) != len(self.param_groups):
-            self._lr_dev = torch.zeros(len(self.param_groups), dtype=torch.float32, device=device)
-            self._lr_seen = [None] * len(self.param_groups)
-            self._tables = {}  # plans hold the array
-        for gi, g in enumerate(self.param_groups):
-            if self._lr_seen[gi] != g["lr"]:
-                self._lr_dev[gi].fill_(g["lr"])
-                self._lr_seen[gi] = g["lr"]
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._lr_seen = [None] * len(self._lr_seen)
+        self._init_plans()
 
     # -- step --------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -389,22 +429,10 @@ class FusedLARS(_MasterWeightsOptimizer):
         key = (tuple(id(p) for p in ps),
                tuple((g["weight_decay"], g["eta"], g["eps"], g["momentum"], g["exclude_bias_and_norm"])
                      for g in self.param_groups))
-        plan = self._tables.get(key)
-        if plan is None:
-            adapt = self._adapt(rows)
-            plan = _ext.require().LarsPlan(
-                [p.numel() for p in ps], [gi for gi, _, _ in rows], adapt, [g["weight_decay"] for _, g, _ in rows],
-                [g["eta"] for _, g, _ in rows], [g["eps"] for _, g, _ in rows], [g["momentum"] for _, g, _ in rows],
-                self._lr_dev, ps[0])
-            # a plan holds a device table and a workspace: keep the few most recent sets (a model whose
-            # set of gradient-less parameters varies would otherwise grow the cache without bound)
-            while len(self._tables) >= self._MAX_PLANS:
-                self._tables.pop(next(iter(self._tables)))
-            self._tables[key] = plan
-        else:
-            self._tables[key] = self._tables.pop(key)  # most recently used last
-        if torch.cuda.is_current_stream_capturing() and plan not in self._captured:
-            self._captured.append(plan)  # a captured graph replays into this plan's memory: never freed
+        plan = self._plan(key, lambda: _ext.require().LarsPlan(
+            [p.numel() for p in ps], [gi for gi, _, _ in rows], self._adapt(rows),
+            [g["weight_decay"] for _, g, _ in rows], [g["eta"] for _, g, _ in rows], [g["eps"] for _, g, _ in rows],
+            [g["momentum"] for _, g, _ in rows], self._lr_dev, ps[0]))
         shadows = [p if m is not None else None for p, m in zip(ps, masters)]
         if emas is None:
             _ext.require().lars_step_list(plan, targets, [p.grad for p in ps], bufs, shadows, self.grad_scale,
@@ -415,10 +443,6 @@ class FusedLARS(_MasterWeightsOptimizer):
         self.last_grad_norm = plan.grad_norm()
         self.last_launches = plan.last_launches()
         return loss
-
-    @staticmethod
-    def _adapt(rows):
-        return [not (g["exclude_bias_and_norm"] and p.ndim <= 1) for _, g, p in rows]
 
     def _reference_step(self, rows, masters, bufs, adapt):
         """The formula of the class docstring in torch: fp32 arithmetic, no host read."""
@@ -452,10 +476,170 @@ class FusedLARS(_MasterWeightsOptimizer):
         self.last_launches = 0
 
 
+class FusedLAMB(_PlannedOptimizer):
+    """LAMB (You et al. 2019): Adam moments with decoupled weight decay, the step of every tensor scaled by the
+    layer-wise trust ratio ``||p|| / ||u||``, and optional clipping by the global gradient norm. Per tensor ``t``
+    stepped in this call (``s`` = ``grad_scale``; ``G``, ``clip`` and ``c`` exactly as in ``FusedLARS``)::
+
+        G     = s * sqrt(sum_t ||g_t||^2)
+        clip  = min(1, max_grad_norm / (G + 1e-6))          (1 when max_grad_norm == 0)
+        c     = s * clip
+        k     = step_t + 1                                   (the tensor's own update count)
+        bc1   = 1 - beta1^k,  bc2 = 1 - beta2^k              (computed as -expm1(k * ln(beta)))
+        gh    = c * g
+        m     = beta1 * m + (1 - beta1) * gh
+        v     = beta2 * v + (1 - beta2) * gh * gh
+        u     = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p
+        trust = ||p|| / ||u||                                (1 when excluded, or ||p|| == 0, or ||u|| == 0)
+        p     = p - lr * trust * u
+
+    With ``exclude_bias_and_norm`` tensors of ``ndim <= 1`` get trust 1 and no weight decay. ``FusedAdamW`` is the
+    same class with trust 1 everywhere. The moments are ``state[p]["exp_avg"]`` and ``state[p]["exp_avg_sq"]``
+    (fp32); ``state[p]["step"]`` is a one-element int32 tensor on the parameter's device that the step itself
+    advances, so a step captured in a HIP graph moves its own bias corrections on every replay. A parameter
+    without a gradient is not stepped: its moments, count and average stay.
+
+    On the GPU a LAMB step is a moments pass (which also sums ``p^2`` and ``u^2`` per block, ``u`` in registers
+    only), one finalize launch (norms, trust, bias corrections, counts) and an apply pass that forms ``u`` again
+    from ``p, m, v``; AdamW is the finalize and one update pass. Clipping adds a gradient square-sum pass (and for
+    LAMB its own finalize) in front. Learning rates come from the device array of ``set_lr``. On CPU, or for
+    low-precision parameters without masters, the same formula runs in torch (also without a host read).
+    """
+
+    _trust = True
+
+    def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.0,
+                 exclude_bias_and_norm: bool = True, grad_scale: float = 1.0, max_grad_norm: float = 0.0,
+                 master_weights: bool = False, ema_decay: float = 0.0):
+        name = type(self).__name__
+        if eps <= 0:
+            raise ValueError(f"{name}: eps > 0 required (with eps = 0 a zero gradient on the first step is 0/0)")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"{name}: betas must be in [0, 1), got {betas}")
+        if lr < 0 or weight_decay < 0 or max_grad_norm < 0:
+            raise ValueError(f"{name}: lr, weight_decay, max_grad_norm >= 0 required")
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                        exclude_bias_and_norm=exclude_bias_and_norm)
+        super().__init__(params, defaults)
+        self.grad_scale = grad_scale
+        self.max_grad_norm = max_grad_norm
+        self.master_weights = master_weights
+        self._init_ema(ema_decay)
+        self._init_plans()
+        self.last_plan = None  # the native plan of the last step (None after a torch step): bias_corrections(), norms()
+        self.last_params: List[torch.Tensor] = []  # the parameters of the last step, in the plan's row order
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        from . import conv as _conv
+
+        _conv.join_all_devices()  # late weight gradients of a backward that raised before its own join
+        rows = []  # (group index, group, parameter), bf16 gradients after fp32 ones: fewest launches
+        for gi, group in enumerate(self.param_groups):
+            rows += [(gi, group, p) for p in group["params"] if p.grad is not None and p.numel() > 0]
+        if not rows:
+            return loss
+        rows.sort(key=lambda r: r[2].grad.dtype != torch.float32)
+        ps = [p for _, _, p in rows]
+        for p in ps:
+            st = self.state[p]
+            if "exp_avg" not in st:
+                st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
+                st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
+                st["step"] = torch.zeros(1, dtype=torch.int32, device=p.device)
+        masters = [self._master(p) for p in ps]
+        ms, vs, steps = ([self.state[p][k] for p in ps] for k in ("exp_avg", "exp_avg_sq", "step"))
+        targets = [m if m is not None else p for p, m in zip(ps, masters)]
+        emas = [self._ema(p, t) for p, t in zip(ps, targets)] if self._ema_on else None
+        dev = ps[0].device
+        on_gpu = all(p.is_cuda and p.grad.is_cuda for p in ps)
+        native = on_gpu and _ext.available() and all(
+            (m is not None or p.dtype == torch.float32) and p.grad.dtype in (torch.float32, torch.bfloat16)
+            for p, m in zip(ps, masters))
+        if on_gpu and _ext.gpu_required() and not _ext.available():
+            _ext.require()
+        self.last_params = ps
+        adapt = self._adapt(rows)
+        if not native:
+            self._reference_step(rows, masters, ms, vs, steps, adapt)
+            if emas is not None:
+                self._reference_ema(emas, targets)
+            return loss
+        self._sync_lr(dev)
+        # the plan (device table + workspaces) depends on which tensors take part, in which order, on their
+        # count tensors (the table holds their addresses) and on their groups' hyper-parameters
+        key = (tuple(id(p) for p in ps), tuple(id(s) for s in steps),
+               tuple((g["weight_decay"], g["betas"], g["eps"], g["exclude_bias_and_norm"]) for g in self.param_groups))
+        C = _ext.require()
+        plan = self._plan(key, lambda: C.AdamPlan(
+            self._trust, [p.numel() for p in ps], [gi for gi, _, _ in rows], adapt,
+            [g["weight_decay"] if a else 0.0 for (_, g, _), a in zip(rows, adapt)],
+            [g["betas"][0] for _, g, _ in rows], [g["betas"][1] for _, g, _ in rows], [g["eps"] for _, g, _ in rows],
+            steps, self._lr_dev, ps[0]))
+        shadows = [p if m is not None else None for p, m in zip(ps, masters)]
+        args = (plan, targets, [p.grad for p in ps], ms, vs, shadows, steps)
+        if emas is None:
+            (C.lamb_step_list if self._trust else C.adamw_step_list)(*args, self.grad_scale, self.max_grad_norm)
+        else:
+            (C.lamb_ema_step_list if self._trust else C.adamw_ema_step_list)(
+                *args, emas, self._sync_omd(dev), self.grad_scale, self.max_grad_norm)
+        self.last_grad_norm = plan.grad_norm() if self.max_grad_norm > 0 else None
+        self.last_launches = plan.last_launches()
+        self.last_plan = plan
+        return loss
+
+    def _reference_step(self, rows, masters, ms, vs, steps, adapt):
+        """The formula of the class docstring in torch: fp32 arithmetic, no host read."""
+        gs = [p.grad.float() for _, _, p in rows]
+        c = self.grad_scale
+        self.last_grad_norm = None
+        if self.max_grad_norm > 0:
+            G = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in gs])) * self.grad_scale
+            c = torch.clamp(self.max_grad_norm / (G + 1e-6), max=1.0) * self.grad_scale
+            self.last_grad_norm = G.reshape(1)
+        for (gi, group, p), g, master, m, v, step, a in zip(rows, gs, masters, ms, vs, steps, adapt):
+            target = master if master is not None else p
+            pf = target if target.dtype == torch.float32 else target.float()
+            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], (group["weight_decay"] if a else 0.0)
+            step.add_(1)
+            k = step.to(torch.float32)
+            bc1, bc2 = (-torch.expm1(k * (math.log(b) if b > 0 else -math.inf)) for b in (b1, b2))
+            gh = g * c
+            m.mul_(b1).add_(gh, alpha=1 - b1)
+            v.mul_(b2).addcmul_(gh, gh, value=1 - b2)
+            u = (m / bc1) / ((v / bc2).sqrt_() + eps)
+            if wd != 0:
+                u.add_(pf, alpha=wd)
+            if self._trust and a:
+                wn, un = torch.linalg.vector_norm(pf), torch.linalg.vector_norm(u)
+                trust = torch.where((wn > 0) & (un > 0), wn / un, torch.ones_like(wn))
+                pf.sub_(u * (lr * trust))
+            else:
+                pf.sub_(u, alpha=lr)
+            if pf is not target:
+                target.copy_(pf)
+            if master is not None:
+                p.copy_(master)
+        self.last_launches = 0
+        self.last_plan = None
+
+
+class FusedAdamW(FusedLAMB):
+    """AdamW (Adam with decoupled weight decay): the formula of ``FusedLAMB`` with trust 1 for every tensor, on
+    the GPU one finalize launch (bias corrections and update counts) and one update pass, without any norm work
+    unless ``max_grad_norm > 0``."""
+
+    _trust = False
+
+
 class ModelEMA:
     """Training with, and evaluation from, the exponential moving average of a model's weights.
 
-    The parameter averages live in the optimizer (``FusedSGD`` / ``FusedLARS`` built with ``ema_decay > 0``, bare
+    The parameter averages live in the optimizer (any fused optimizer here built with ``ema_decay > 0``, bare
     or inside a ``DistributedOptimizer``), which advances them inside its update launches; this class adds the
     averages of the model's floating-point buffers (BatchNorm running statistics; integer buffers such as
     ``num_batches_tracked`` are left alone), the decay schedule, and the exchange of weights and averages for

@@ -27,6 +27,9 @@ Differences by design:
 * optional weight averaging (``--ema_decay``, ``--ema_warmup``): the optimizer's update kernels also advance an
   exponential moving average of every weight (ops/optim.py ``ModelEMA``), every evaluation runs a second time
   from the averages (``eval_ema`` lines), and checkpoints carry them; without the flag nothing of it runs;
+* optional Adam-family optimizers (``--optimizer lamb`` / ``adamw`` with ``--beta1``, ``--beta2``, ``--opt_eps``): the
+  fused LAMB / AdamW of ops/optim.py under the same schedule, clipping (``--max_grad_norm``), weight averaging and
+  checkpoint code as LARS; with ``sgd`` or ``lars`` nothing of it runs;
 * optional staged and device-resident data (``--staged_dir``, ``--resident 1``, both on top of ``--augment
   standard``): the ImageNet staging images come from the files of ``distributed_learning_amd.stage`` instead of a
   per-epoch JPEG decode, and with ``--resident 1`` the rank's shard lives on the device (``data.ResidentStore``),
@@ -57,7 +60,7 @@ from .models import get_spec
 from .ops import augment as aug
 from .ops import nn as dnn
 from .ops.loss import cross_entropy, cross_entropy_mix, cross_entropy_with_metrics
-from .ops.optim import FusedLARS, FusedSGD, ModelEMA, poly_warmup_lr
+from .ops.optim import FusedAdamW, FusedLAMB, FusedLARS, FusedSGD, ModelEMA, poly_warmup_lr
 from .timing import EventTimers, Timers
 from .utils.log import Level, print_d
 
@@ -305,8 +308,15 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, map_location=No
 
 
 def make_optimizer(config, params, master_weights: bool):
-    """``--optimizer sgd`` (default): the reference's momentum SGD; ``lars``: the fused LARS."""
+    """``--optimizer sgd`` (default): the reference's momentum SGD; ``lars``: the fused LARS; ``lamb`` / ``adamw``:
+    the fused LAMB / AdamW (``--beta1``, ``--beta2``, ``--opt_eps``; ``--momentum`` is not theirs)."""
     ema = dict(ema_decay=config.ema_decay) if getattr(config, "ema_decay", 0.0) > 0 else {}
+    kind = getattr(config, "optimizer", "sgd")
+    if kind in ("lamb", "adamw"):
+        return (FusedLAMB if kind == "lamb" else FusedAdamW)(
+            params, lr=config.lr, betas=(getattr(config, "beta1", 0.9), getattr(config, "beta2", 0.999)),
+            eps=getattr(config, "opt_eps", 1e-6), weight_decay=config.weight_decay,
+            max_grad_norm=getattr(config, "max_grad_norm", 0.0), master_weights=master_weights, **ema)
     if getattr(config, "optimizer", "sgd") == "lars":
         return FusedLARS(params, lr=config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
                          eta=getattr(config, "lars_eta", 1e-3), max_grad_norm=getattr(config, "max_grad_norm", 0.0),
@@ -329,7 +339,7 @@ def lr_schedule(config) -> Optional[Callable[[int], float]]:
 
 def set_lr(optimizer, lr: float) -> None:
     if hasattr(optimizer, "set_lr"):
-        optimizer.set_lr(lr)  # FusedLARS: also the device scalar its kernels read
+        optimizer.set_lr(lr)  # FusedLARS / FusedLAMB / FusedAdamW: also the device scalar their kernels read
     else:
         for group in optimizer.param_groups:
             group["lr"] = lr

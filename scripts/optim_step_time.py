@@ -1,8 +1,10 @@
-"""Step time of FusedSGD and FusedLARS on ResNet-50's parameter shapes (bf16 gradients, fp32 masters).
+"""Step time of FusedSGD, FusedLARS, FusedLAMB and FusedAdamW on ResNet-50's parameter shapes (bf16 gradients,
+fp32 masters), and of torch.optim.AdamW(fused=True) on fp32 copies of the same tensors where this torch has it.
 
 Each optimizer: 5 warm-up steps, then 20 steps timed one by one with HIP events; prints one JSON line per
-optimizer with the median and the launch count of a step, then the device and its clocks. The gradients
-are fixed random tensors: only the optimizer runs between the events.
+optimizer with the median and the launch count of a step, the device time of every kernel and the rate it
+reaches against the bytes it has to move (``_BYTES``), then the device and its clocks. The gradients are fixed
+random tensors: only the optimizer runs between the events.
 
     python scripts/optim_step_time.py [--steps 20] [--warmup 5]
 """
@@ -20,7 +22,31 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_learning_amd.models import resnet50  # noqa: E402
 from distributed_learning_amd.ops import _ext  # noqa: E402
 from distributed_learning_amd.ops import nn as dnn  # noqa: E402
-from distributed_learning_amd.ops.optim import FusedLARS, FusedSGD  # noqa: E402
+from distributed_learning_amd.ops.optim import FusedAdamW, FusedLAMB, FusedLARS, FusedSGD  # noqa: E402
+
+
+# Bytes per parameter element a kernel has to move, (bf16 gradient + bf16 shadow, fp32 gradient and no shadow):
+# fp32 p, m, v (and momentum) at 4 B each way, the gradient read once, the shadow written once.
+_BYTES = {
+    "sgd_list_kernel": (20, 20),           # r p g m, w p m shadow
+    "lars_list_kernel": (20, 20),
+    "sqsum_list_kernel": (6, 8),           # r p g (LARS); the clipping pass of LAMB / AdamW reads g only
+    "lamb_moments_list_kernel": (22, 24),  # r p g m v, w m v
+    "lamb_apply_list_kernel": (18, 16),    # r p m v, w p shadow
+    "adamw_list_kernel": (28, 28),         # r p g m v, w p m v shadow
+}
+
+
+def _rates(kernel_us, params, grad_only_sqsum):
+    """GB/s of every kernel of ``_BYTES`` over its launches of one step (all gradient dtypes together)."""
+    n16 = sum(p.numel() for p in params if p.grad.dtype == torch.bfloat16)
+    n32 = sum(p.numel() for p in params if p.grad.dtype == torch.float32)
+    out = {}
+    for name, us in kernel_us.items():
+        if name in _BYTES and us > 0:
+            b16, b32 = (2, 4) if name == "sqsum_list_kernel" and grad_only_sqsum else _BYTES[name]
+            out[name] = round((b16 * n16 + b32 * n32) / us * 1e-3, 1)
+    return out
 
 
 def _model(dev):
@@ -103,26 +129,50 @@ def main():
     a = ap.parse_args()
     _ext.require()
     dev = torch.device("cuda:0")
-    rows = []
-    for name in ("FusedSGD", "FusedLARS"):
+    rows = {}
+    makers = {
+        "FusedSGD": lambda ps: FusedSGD(ps, lr=0.01, momentum=0.9, weight_decay=1e-4, master_weights=True),
+        "FusedLARS": lambda ps: FusedLARS(ps, lr=0.01, momentum=0.9, weight_decay=1e-4, max_grad_norm=1.0,
+                                          master_weights=True),
+        "FusedLAMB": lambda ps: FusedLAMB(ps, lr=0.002, weight_decay=1e-2, master_weights=True),
+        "FusedLAMB+clip": lambda ps: FusedLAMB(ps, lr=0.002, weight_decay=1e-2, max_grad_norm=1.0,
+                                               master_weights=True),
+        "FusedAdamW": lambda ps: FusedAdamW(ps, lr=0.001, weight_decay=1e-2, master_weights=True),
+        "FusedAdamW+clip": lambda ps: FusedAdamW(ps, lr=0.001, weight_decay=1e-2, max_grad_norm=1.0,
+                                                 master_weights=True),
+    }
+    stock = "torch.optim.AdamW(fused=True) fp32"
+    try:
+        # capturable: its step counts live on the device, so that its step can be replayed from a graph too
+        torch.optim.AdamW([torch.zeros(1, device=dev, requires_grad=True)], fused=True, capturable=True)
+        makers[stock] = lambda ps: torch.optim.AdamW(ps, lr=0.001, weight_decay=1e-2, fused=True, capturable=True)
+    except (RuntimeError, TypeError, ValueError) as e:
+        print(json.dumps({"optimizer": stock, "unavailable": str(e)[:200]}), flush=True)
+    for name, make in makers.items():
         m = _model(dev)
         params = list(m.parameters())
-        if name == "FusedSGD":
-            opt = FusedSGD(params, lr=0.01, momentum=0.9, weight_decay=1e-4, master_weights=True)
-        else:
-            opt = FusedLARS(params, lr=0.01, momentum=0.9, weight_decay=1e-4, max_grad_norm=1.0, master_weights=True)
+        if name == stock:  # the stock alternative has no masters: fp32 tensors and fp32 gradients
+            grads = [p.grad.float() for p in params]
+            params = [p.detach().float().requires_grad_() for p in params]
+            for p, g in zip(params, grads):
+                p.grad = g
+        opt = make(params)
         ms = _time(opt, a.steps, a.warmup)
         launches, kernel_us = _launches(opt)
         gms = _time_graphed(opt, a.steps)
         n = sum(p.numel() for p in params)
-        rows.append({"optimizer": name, "tensors": len(params), "params": n, "median_ms": round(statistics.median(ms), 4),
-                     "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
-                     "graph_replay_median_ms": round(statistics.median(gms), 4),
-                     "launches_per_step": launches, "kernel_us_per_step": kernel_us,
-                     "steps": a.steps, "warmup": a.warmup})
-        print(json.dumps(rows[-1]), flush=True)
-    print(json.dumps({"lars_over_sgd": round(rows[1]["median_ms"] / rows[0]["median_ms"], 3),
-                      "lars_over_sgd_graph": round(rows[1]["graph_replay_median_ms"] / rows[0]["graph_replay_median_ms"], 3),
+        rows[name] = {"optimizer": name, "tensors": len(params), "params": n,
+                      "median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4),
+                      "max_ms": round(max(ms), 4), "graph_replay_median_ms": round(statistics.median(gms), 4),
+                      "launches_per_step": launches, "kernel_us_per_step": kernel_us,
+                      "kernel_gbps": _rates(kernel_us, params, name.startswith(("FusedLAMB", "FusedAdamW"))),
+                      "steps": a.steps, "warmup": a.warmup}
+        print(json.dumps(rows[name]), flush=True)
+        del opt, m, params
+    sgd = rows["FusedSGD"]
+    print(json.dumps({**{f"{k}_over_sgd": round(r["median_ms"] / sgd["median_ms"], 3) for k, r in rows.items() if r is not sgd},
+                      **{f"{k}_over_sgd_graph": round(r["graph_replay_median_ms"] / sgd["graph_replay_median_ms"], 3)
+                         for k, r in rows.items() if r is not sgd},
                       "device": torch.cuda.get_device_name(0), "clocks": _clocks()}), flush=True)
 
 
