@@ -68,6 +68,9 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
         self.stride = stride
         self.defer_output = False  # set by ResNet for every bottleneck followed by another
+        # hook tables of the other modules that are handed this block's output; like defer_output, set by
+        # ResNet._chain_bottlenecks for the modules it has then: call it again after replacing a block or a layer
+        self.output_watch = ()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # conv1 forwards x as a second output that feeds the identity branch (or the downsample conv),
@@ -84,7 +87,10 @@ class Bottleneck(nn.Module):
         # pass to that block's conv1 GEMM (ops/bn_act.py PendingApply); nothing else may observe it. The same for
         # bn2, whose only consumer is conv3 (the streaming GEMM applies it at stages 1-2)
         observed = bool(self._forward_hooks or self._forward_pre_hooks or nn.modules.module._global_forward_hooks)
-        defer = self.defer_output and not observed
+        # the block output is also handed to global pre-hooks, to pre-hooks of the next block and, at a stage's
+        # end, to hooks of the enclosing / next Sequential
+        defer = self.defer_output and not (observed or nn.modules.module._global_forward_pre_hooks
+                                           or any(self.output_watch))
         out = dnn.conv_bn_act(out, self.conv2, self.bn2, relu=True, defer=not observed and knobs.flag("DEFER_MID"))
         if self.downsample is None:
             return dnn.conv_bn_act(out, self.conv3, self.bn3, relu=True, residual=xa, defer=defer)
@@ -154,10 +160,14 @@ class ResNet(nn.Module):
 
     def _chain_bottlenecks(self) -> None:
         """Mark every bottleneck whose output feeds another bottleneck (all but the network's last)."""
-        blocks = [b for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer]
-        for b, nxt in zip(blocks, blocks[1:]):
+        layers = (self.layer1, self.layer2, self.layer3, self.layer4)
+        blocks = [(b, layer) for layer in layers for b in layer]
+        for (b, layer), (nxt, nxt_layer) in zip(blocks, blocks[1:]):
             if isinstance(b, Bottleneck):
                 b.defer_output = isinstance(nxt, Bottleneck)
+                b.output_watch = (nxt._forward_pre_hooks,)
+                if nxt_layer is not layer:
+                    b.output_watch += (layer._forward_hooks, nxt_layer._forward_pre_hooks)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = dnn.conv_bn_act_maxpool(x, self.conv1, self.bn1, self.maxpool)

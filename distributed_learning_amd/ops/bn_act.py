@@ -3,8 +3,8 @@
 Used by :func:`distributed_learning_amd.ops.nn.bn_act` when the ``native`` backend is selected.
 Semantics match ``relu(batch_norm(x, training=bn.training) + residual)`` with PyTorch's running
 statistics update (momentum, unbiased running variance). Inputs that the kernel does not cover
-(channel counts not divisible by 8, non-channels_last layouts, cumulative-average momentum) take
-the stock PyTorch path.
+(channel counts not divisible by 8, non-channels_last layouts, cumulative-average momentum, an
+eval-mode BN whose backward will run) take the stock PyTorch path.
 """
 from __future__ import annotations
 
@@ -17,6 +17,22 @@ from . import limits as _limits
 
 
 MASK_NONE, MASK_RECOMPUTE, MASK_BITS, MASK_Y = 0, 1, 2, 3
+
+
+# The autograd engine's id of the running backward pass: a private torch binding (verified with torch 2.10).
+# Without it a hand-off could not tell its own pass from an earlier one, so its absence is an error, not a silent
+# fallback -- raised where the first hand-off asks for the id, so that inference and the stock paths, which hand
+# nothing over, still run on such a build.
+_current_graph_task_id = getattr(torch._C, "_current_graph_task_id", None)
+
+
+def graph_task() -> int:
+    """Id of the running backward pass (the autograd engine's graph task; -1 outside one). State that one
+    autograd node parks for another is valid within the pass that parked it only."""
+    if _current_graph_task_id is None:
+        raise RuntimeError("this torch build has no torch._C._current_graph_task_id; the fused BN hand-offs need "
+                           "it to confine parked state to one backward pass (verified with torch 2.10)")
+    return _current_graph_task_id()
 
 
 class BNLink:
@@ -51,12 +67,23 @@ class ResidualLink:
     The residual's gradient is dy * relu'(out) — dy masked by the forward's 1-bit mask. Instead of
     the BN backward writing it out (a full tensor write + read), it hands (dy, mask) to the forking
     conv (ops/conv.py::_Conv1x1Fork), whose dgrad epilogue adds dy where the mask bit is set. Valid
-    only when the residual tensor is that fork's identity output (checked at forward time)."""
+    only when the residual tensor is that fork's identity output (checked at forward time), and only within the
+    backward pass that handed it over: a pass that ran the BN but not the fork (``autograd.grad`` with pruned
+    inputs) leaves it behind, and a later pass must not add it (take() drops it)."""
 
-    __slots__ = ("dy", "mask")
+    __slots__ = ("dy", "mask", "task")
 
     def __init__(self):
-        self.dy = self.mask = None
+        self.dy = self.mask = self.task = None
+
+    def hand(self, dy, mask) -> None:
+        self.dy, self.mask, self.task = dy, mask, graph_task()
+
+    def take(self):
+        """(dy, mask) handed over in the running backward pass, else (None, None); cleared either way."""
+        dy, mask, task = self.dy, self.mask, self.task
+        self.dy = self.mask = self.task = None
+        return (dy, mask) if dy is not None and task == graph_task() else (None, None)
 
 
 class PendingApply:
@@ -155,7 +182,7 @@ class _BNAct(torch.autograd.Function):
         # mask (ReLU after the residual add) -- the output y is never re-read.
         ctx.mask_mode = MASK_NONE if not relu else (MASK_BITS if ctx.has_res else MASK_RECOMPUTE)
         m = mask if mask is not None and mask.numel() else None
-        ctx.save_for_backward(x, ws, weight, m)
+        ctx.save_for_backward(x, ws, weight, m, residual if ctx.rlink is not None else None)
         ctx.link = BNLink(x, ws, m, ctx.mask_mode) if training and x.dtype == torch.bfloat16 else None
         # the producing 1x1 conv (the block's conv3) applies this BN's backward itself (ops/conv.py DualBNLink):
         # a bit-mask ReLU after the residual add, the residual gradient handed to the fork; bf16
@@ -168,24 +195,25 @@ class _BNAct(torch.autograd.Function):
     def backward(ctx, dy):
         if not ctx.training:
             raise RuntimeError("fused BN backward in eval mode is not supported; use the torch backend")
-        x, ws, weight, mask = ctx.saved_tensors
+        x, ws, weight, mask, res = ctx.saved_tensors
         C = _ext.require()
         ext = ctx.link.take(dy) if ctx.link is not None else None
         rl = ctx.rlink
-        if ctx.dlink is not None and ctx.dlink.can_park(x):
+        if rl is not None and (res.retains_grad or getattr(res, "_backward_hooks", None)):
+            rl = None  # an observer of the identity's gradient must see the real one: write it out
+        if ctx.dlink is not None and rl is not None and ctx.dlink.can_park(x):
             # reduction + finalize only; the conv backward applies (dy, x, mask, ws) in its own kernel
             dy = dy.contiguous(memory_format=torch.channels_last)
             _, _, dg, db = C.bn_act_bwd(dy, None, mask, x, ws, weight, ctx.mask_mode, False, ext, False)
             dx = ctx.dlink.park(dy, x, ws, mask, weight, ctx.mask_mode)
-            if rl is not None:
-                rl.dy, rl.mask = dy, mask
+            rl.hand(dy, mask)
             need = ctx.needs_input_grad
             return (dx, dg if need[1] else None, db if need[2] else None, None,
                     None, None, None, None, None, None, None, None, None, None)
         dx, dres, dg, db = C.bn_act_bwd(dy, None, mask, x, ws, weight, ctx.mask_mode, ctx.has_res and rl is None, ext)
         if rl is not None:  # the forking conv adds dy (masked) in its dgrad epilogue
-            rl.dy = dy.contiguous(memory_format=torch.channels_last) if dy.dim() == 4 else dy.contiguous()
-            rl.mask = mask if ctx.mask_mode == MASK_BITS else None
+            rl.hand(dy.contiguous(memory_format=torch.channels_last) if dy.dim() == 4 else dy.contiguous(),
+                    mask if ctx.mask_mode == MASK_BITS else None)
             dres = None
         need = ctx.needs_input_grad
         return (dx, dg if need[1] else None, db if need[2] else None, dres if ctx.has_res else None,
@@ -305,7 +333,11 @@ def fused_bn_act(x: torch.Tensor, bn: nn.BatchNorm2d, relu: bool = True, residua
     epilogue (training mode only) — the statistics pass over ``x`` is then skipped. ``defer``: with ReLU (and
     optionally a residual), the output may be left for its consumer to write (PendingApply; inside a
     deferral_scope)."""
-    if not supported(x, bn, residual):
+    # a BN normalising with its running statistics whose backward will run (frozen-BN fine-tuning): the fused
+    # backward is the training-mode one only
+    frozen = (not bn.training and bn.track_running_stats and torch.is_grad_enabled()
+              and any(t is not None and t.requires_grad for t in (x, residual, bn.weight, bn.bias)))
+    if frozen or not supported(x, bn, residual):
         y = bn(x)
         if residual is not None:
             y = y + residual

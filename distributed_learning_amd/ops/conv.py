@@ -25,6 +25,7 @@ from . import limits as _limits
 from .bn_act import ResidualLink
 from .bn_act import pending_of
 from .bn_act import bn_link_of as _bn_link_of
+from .bn_act import graph_task as _graph_task
 
 # Fuse the backward reduction of a producing BatchNorm into this conv's dgrad epilogue (BNLink).
 # "0" (default) off, "1" every dgrad, "stream" only the short-K 1x1 data gradients the persistent
@@ -252,12 +253,16 @@ class DualBNLink:
     with the conv output itself as an input (the engine captures the placeholder; its introspection,
     ``torch._C._will_engine_execute_node``, reports the producing node as executed either way). Code that
     differentiates with respect to a conv output turns the hand-offs off (``DUAL_BN`` / ``STEM_BN`` here,
-    ``DLA_STEM_BN=0``) or registers a hook on it."""
+    ``DLA_STEM_BN=0``) or registers a hook on it.
 
-    __slots__ = ("ph", "dout", "ybn", "ws", "mask", "weight", "mode", "claimed")
+    A park is valid within the backward pass that made it only: a pass that ran the BN but pruned the conv
+    (``autograd.grad(loss, [bn.weight], retain_graph=True)``) leaves one behind, which parked() drops instead of
+    letting a later pass add it to a fresh gradient."""
+
+    __slots__ = ("ph", "dout", "ybn", "ws", "mask", "weight", "mode", "claimed", "task")
 
     def __init__(self):
-        self.ph = self.dout = self.ybn = self.ws = self.mask = self.weight = self.mode = None
+        self.ph = self.dout = self.ybn = self.ws = self.mask = self.weight = self.mode = self.task = None
         self.claimed = False
 
     def claim(self) -> bool:
@@ -270,18 +275,25 @@ class DualBNLink:
     def observed(y) -> bool:
         return bool(y.retains_grad or getattr(y, "_backward_hooks", None))
 
+    def parked(self) -> bool:
+        """Whether the running backward pass parked here; what an earlier pass left behind is dropped."""
+        if self.ph is not None and self.task != _graph_task():
+            self.take()
+        return self.ph is not None
+
     def can_park(self, y) -> bool:
-        return self.ph is None and not self.observed(y)
+        return not self.parked() and not self.observed(y)
 
     def park(self, dout, ybn, ws, mask, weight, mode=2):
         assert self.can_park(ybn), "DualBNLink.park: check can_park first"
         self.dout, self.ybn, self.ws, self.mask, self.weight, self.mode = dout, ybn, ws, mask, weight, mode
+        self.task = _graph_task()
         self.ph = torch.zeros((), dtype=ybn.dtype, device=ybn.device).expand(ybn.shape)
         return self.ph
 
     def take(self):
         out = (self.ph, self.dout, self.ybn, self.ws, self.mask, self.weight, self.mode)
-        self.ph = self.dout = self.ybn = self.ws = self.mask = self.weight = self.mode = None
+        self.ph = self.dout = self.ybn = self.ws = self.mask = self.weight = self.mode = self.task = None
         return out
 
     def materialise(self, C, dy, parked):
@@ -332,7 +344,7 @@ class _Conv1x1(torch.autograd.Function):
         x, w2 = ctx.saved_tensors
         odt = ctx.wdtype if ctx.wdtype in (torch.float32, torch.bfloat16) else torch.float32
         dl = ctx.dlink
-        if dl is not None and dl.ph is not None:
+        if dl is not None and dl.parked():
             parked = dl.take()
             ph, dout, ybn, ws, mask, weight, _ = parked
             if (dy is not None and dy.data_ptr() == ph.data_ptr() and dy.stride() == ph.stride()
@@ -452,11 +464,10 @@ class _Conv1x1Fork(torch.autograd.Function):
             dsub = dsub.contiguous(memory_format=torch.channels_last).to(torch.bfloat16)
         rl = ctx.rlink
         amask = None
-        if rl is not None and rl.dy is not None:
+        rdy, rmask = rl.take() if rl is not None else (None, None)
+        if rdy is not None:
             # identity gradient handed over by the BN(+residual)+ReLU that consumed the identity:
             # dy where the forward's ReLU bit is set (added in the epilogue below)
-            rdy, rmask = rl.dy, rl.mask
-            rl.dy = rl.mask = None
             if dident is None:
                 dident, amask = rdy, rmask
             else:  # the identity had other consumers too: materialise the masked gradient
@@ -714,12 +725,13 @@ class StemBNLink(DualBNLink):
     def park(self, dout, pos, ybn, ws, weight, geom):
         assert self.can_park(ybn), "StemBNLink.park: check can_park first"
         self.dout, self.pos, self.ybn, self.ws, self.weight, self.geom = dout, pos, ybn, ws, weight, geom
+        self.task = _graph_task()
         self.ph = torch.zeros((), dtype=ybn.dtype, device=ybn.device).expand(ybn.shape)
         return self.ph
 
     def take(self):
         out = (self.ph, self.dout, self.pos, self.ybn, self.ws, self.weight, self.geom)
-        self.ph = self.dout = self.pos = self.ybn = self.ws = self.weight = self.geom = None
+        self.ph = self.dout = self.pos = self.ybn = self.ws = self.weight = self.geom = self.task = None
         return out
 
     def materialise(self, C, dy, parked):
@@ -762,7 +774,7 @@ class _StemConv(torch.autograd.Function):
         (xs,) = ctx.saved_tensors
         dw = None
         sl = ctx.slink
-        if sl is not None and sl.ph is not None:
+        if sl is not None and sl.parked():
             parked = sl.take()
             ph, dout, pos, ybn, ws = parked[:5]
             if not ctx.needs_input_grad[1]:

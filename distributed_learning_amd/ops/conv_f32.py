@@ -33,12 +33,16 @@ STEM_NATIVE = True
 
 def supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
     """A conv this path runs: fp32 channels_last CUDA input, groups 1, no dilation, no bias, channels
-    (after padding 3 -> 4) and Cout multiples of 4, stride 1 whenever the input needs a gradient."""
+    (after padding 3 -> 4) and Cout multiples of 4, padding at most kernel - 1 (the data gradient pads by
+    kernel - 1 - padding); whenever the input needs a gradient, stride 1 and channels a multiple of 4 (the data
+    gradient's output channels)."""
     if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and conv.weight.dtype == torch.float32):
         return False
     if conv.groups != 1 or conv.dilation != (1, 1) or conv.bias is not None:
         return False
     if conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] or conv.padding[0] != conv.padding[1]:
+        return False
+    if conv.padding[0] > conv.kernel_size[0] - 1:
         return False
     cin, cout = x.shape[1], conv.out_channels
     oh = (x.shape[2] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
@@ -52,7 +56,7 @@ def supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
         return _limits.divisors_ok(dims, "fp32 conv")
     if cout % 4 or not (cin % 4 == 0 or (cin == 3 and STEM_NATIVE)):
         return False
-    if conv.stride[0] != 1 and x.requires_grad:
+    if (conv.stride[0] != 1 or cin % 4) and x.requires_grad:
         return False
     return x.shape[0] * oh * ow < (1 << 24) and x.numel() * 4 < (1 << 31) and _limits.divisors_ok(dims, "fp32 conv")
 
