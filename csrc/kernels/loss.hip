@@ -83,16 +83,18 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
 void launch_xent_fwd(const void* logits, const int64_t* target, float* ws, float* loss_out, int B, int C, int dtype,
                      hipStream_t stream) {
   dim3 grid((B + kXWaves - 1) / kXWaves), block(kXWaves * 64);
-  dispatch_dtype(dtype, [&](auto t) {
-    using T = tag_t<decltype(t)>;
-    hipLaunchKernelGGL(xent_rows_kernel<T>, grid, block, 0, stream, (const T*)logits, target, ws, B, C);
-  });
+  if (B > 0)  // an empty batch has no rows to launch; the mean kernel still writes NaN and a count of 0
+    dispatch_dtype(dtype, [&](auto t) {
+      using T = tag_t<decltype(t)>;
+      hipLaunchKernelGGL(xent_rows_kernel<T>, grid, block, 0, stream, (const T*)logits, target, ws, B, C);
+    });
   hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, stream, ws, loss_out, B);
 }
 
 void launch_xent_bwd(const void* logits, const int64_t* target, const float* ws, const float* loss_out,
                      const float* gout, void* dlogits, int B, int C, int dtype, hipStream_t stream) {
   const int64_t total = (int64_t)B * C;
+  if (total <= 0) return;
   int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
   dispatch_dtype(dtype, [&](auto t) {
     using T = tag_t<decltype(t)>;

@@ -784,30 +784,6 @@ void augment_mix_gather_(at::Tensor store, at::Tensor index, at::Tensor out, at:
                             bias.data_ptr<float>(), d.N, d.Hs, d.Ws, d.Ho, d.Wo, (int)pad, blend, current_stream(out));
 }
 
-std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor target) {
-  check_dev(logits, "logits");
-  check_dev(target, "target");
-  TORCH_CHECK(logits.dim() == 2, "xent_fwd: logits must be [B, C]");
-  TORCH_CHECK(target.scalar_type() == at::kLong && target.numel() == logits.size(0), "xent_fwd: bad target");
-  const int B = (int)logits.size(0), C = (int)logits.size(1);
-  auto f32 = logits.options().dtype(at::kFloat);
-  auto ws = at::empty({3 * (int64_t)B}, f32);
-  auto loss = at::empty({2}, f32);
-  launch_xent_fwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), loss.data_ptr<float>(), B, C,
-                  dtype_code(logits), current_stream(logits));
-  return {loss, ws};
-}
-
-at::Tensor xent_bwd(at::Tensor logits, at::Tensor target, at::Tensor ws, at::Tensor loss, at::Tensor gout) {
-  check_dev(logits, "logits");
-  auto d = at::empty_like(logits);
-  const int B = (int)logits.size(0), C = (int)logits.size(1);
-  auto g = gout.to(at::kFloat).contiguous();
-  launch_xent_bwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), loss.data_ptr<float>(),
-                  g.data_ptr<float>(), d.data_ptr(), B, C, dtype_code(logits), current_stream(logits));
-  return d;
-}
-
 // Counts are carried as floats: below 2^24 rows and classes every count and rank is exact.
 constexpr int64_t kXentMaxDim = int64_t(1) << 24;
 
@@ -821,6 +797,33 @@ static void check_xent_args(const at::Tensor& logits, const at::Tensor& target, 
   TORCH_CHECK(logits.size(1) >= 1, op, ": no classes");
   TORCH_CHECK(logits.size(0) < kXentMaxDim && logits.size(1) < kXentMaxDim, op, ": B and C must be below 2^24");
   TORCH_CHECK(eps >= 0.0 && eps < 1.0, op, ": label smoothing must be in [0, 1), got ", eps);
+}
+
+std::vector<at::Tensor> xent_fwd(at::Tensor logits, at::Tensor target) {
+  check_xent_args(logits, target, 0.0, "xent_fwd");
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto ws = at::empty({3 * (int64_t)B}, f32);
+  auto loss = at::empty({2}, f32);
+  launch_xent_fwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), loss.data_ptr<float>(), B, C,
+                  dtype_code(logits), current_stream(logits));
+  return {loss, ws};
+}
+
+at::Tensor xent_bwd(at::Tensor logits, at::Tensor target, at::Tensor ws, at::Tensor loss, at::Tensor gout) {
+  check_xent_args(logits, target, 0.0, "xent_bwd");
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  check_dev(ws, "ws");
+  check_dev(loss, "loss");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() == 3 * (int64_t)B && ws.is_contiguous(),
+              "xent_bwd: bad workspace");
+  TORCH_CHECK(loss.scalar_type() == at::kFloat && loss.numel() == 2 && loss.is_contiguous(), "xent_bwd: bad loss");
+  TORCH_CHECK(gout.is_cuda() && gout.numel() == 1, "xent_bwd: gout must be one value on the GPU");
+  auto g = gout.to(at::kFloat).contiguous();
+  auto d = at::empty_like(logits);
+  launch_xent_bwd(logits.data_ptr(), target.data_ptr<int64_t>(), ws.data_ptr<float>(), loss.data_ptr<float>(),
+                  g.data_ptr<float>(), d.data_ptr(), B, C, dtype_code(logits), current_stream(logits));
+  return d;
 }
 
 std::vector<at::Tensor> xent_metrics_fwd(at::Tensor logits, at::Tensor target, double eps, int64_t k) {

@@ -29,6 +29,7 @@ class _XEnt(torch.autograd.Function):
     def forward(ctx, logits, target):
         C = _ext.require()
         logits = logits.contiguous()
+        target = target.contiguous()
         loss, ws = C.xent_fwd(logits, target)
         ctx.save_for_backward(logits, target, ws, loss)
         return loss[0]
